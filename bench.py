@@ -7,10 +7,16 @@ what FlowModel.sample does per loop iteration (flow_model.py:287-343).  Inputs (
 weights, state) are resident in HBM when the timed region starts; encode() and the final D2H are
 outside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4|cfg2|cfg3|cfg5] [--precision fp32|f16]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4|cfg2|cfg3|cfg5] [--precision fp32|f16] [--full] [--dump-outputs DIR]
 Default workload: the 128-residue configuration BASELINE.json's metric / target is quoted on (per-GPU share of
-configs[3]: B=64 x L=128, fp32-parity arithmetic); at N=1 the line also carries a "secondary" entry for
-configs[1] (B=16 x L=64).
+configs[3]: B=64 x L=128, fp32-parity arithmetic).
+A plain run sets up, runs W warm-up and K timed steps and prints the headline line (value, ms_per_step, set-up phases).
+--full adds everything else the line used to carry: the per-kernel event timing and the rooflines built on it, the clock
+under load, the final-state check, the trajectory D2H, and at N=1 the "secondary" entry for configs[1] (B=16 x L=64),
+the other precision modes / configurations, the per-call accounting and the CPU baseline.
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32): the sampler's
+final state (rotmats, trans, angles, seqs, seqs_simplex; [B, L, ...]) or, for cfg5, the six losses and every parameter
+gradient.  Inputs are seeded, so two builds run with the same arguments can be compared output for output.
 For N>1 either launch with torch.distributed.run (one rank per GPU), or run `python bench.py --gpus N` directly:
 without WORLD_SIZE in the environment it re-executes itself under torch.distributed.run with N ranks on
 127.0.0.1.  The path shards over independent samples: every rank runs the same per-GPU workload (weak scaling),
@@ -149,8 +155,10 @@ class _Clock:
         self.t = now
 
 
-def run_sampler(wl, K, W, dev, dist, rank, world, use_graph, precision, time_kernels=True):
-    """W warm-up + K timed steps of the sampler on this rank's shard; returns (elapsed_s_max_over_ranks, info)."""
+def run_sampler(wl, K, W, dev, dist, rank, world, use_graph, precision, time_kernels=True, full=True, want_final=False):
+    """W warm-up + K timed steps of the sampler on this rank's shard; returns (elapsed_s_max_over_ranks, info).
+    full=False: nothing after the timed steps but the closing all-gather (N > 1) -- no final-state check, clock read-out,
+    trajectory D2H or per-kernel timing.  want_final: info["final"] = the last step's state as CPU tensors (all ranks' samples)."""
     from pepflowww_amd import synth, _capi
     NS = K + W
     model, sd = get_model(dev, precision)
@@ -209,15 +217,21 @@ def run_sampler(wl, K, W, dev, dist, rank, world, use_graph, precision, time_ker
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        from pepflowww_amd.distributed import all_gather_final_state, unpack_state, _final_state_of
         if dist is not None:
             tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
             # closing all-gather of the final state (one collective per sample() call)
-            from pepflowww_amd.distributed import all_gather_final_state
-            all_gather_final_state(smp)
-        info["validity"] = check_final_state(smp, batch, NS)
+            final = all_gather_final_state(smp)
+        elif want_final:
+            final = unpack_state(_final_state_of(smp))
+        if want_final:
+            info["final"] = {k: v.cpu() for k, v in final.items()}   # the last trajectory slot = the last timed step
         info["launches_per_step"] = sum(e.n_launches + 1 for e in engines)
+        if not full:
+            return elapsed, info
+        info["validity"] = check_final_state(smp, batch, NS)
         if wl.get("read_sclk"):
             info["sclk"] = sclk_under_load(smp, use_graph)
         ck = _Clock()
@@ -264,6 +278,21 @@ def run_sampler(wl, K, W, dev, dist, rank, world, use_graph, precision, time_ker
                     del d["per_bucket"]
             info["kernel_us"] = per
     return elapsed, info
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (sequence ids are exact in it), at most DUMP_MAX_BYTES in all."""
+    import numpy as np
+    arrs = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def _parse_engine_opts(items):
@@ -385,6 +414,9 @@ def main():
     ap.add_argument("--no-per-call", action="store_true", help="skip the inference.py-style per-call accounting")
     ap.add_argument("--per-call-steps", type=int, default=200)
     ap.add_argument("--engine-opt", action="append", default=[], metavar="NAME=0|1", help="force a plan choice of DenoiseEngine (A/B runs), e.g. --engine-opt et_v5=0")
+    ap.add_argument("--full", action="store_true", help="also per-kernel timing, rooflines, clock read-out, final-state check, trajectory D2H, "
+                    "the secondary / modes / per-call entries and the CPU baseline (the --no-* options prune these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     _parse_engine_opts(args.engine_opt)
     if os.environ.get("PF_BENCH_O_PREMUL") == "0":              # same-box A/B of the folded value projection (DenoiseEngine.O_PREMUL)
@@ -399,10 +431,11 @@ def main():
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched the way the driver may launch it (`python bench.py --gpus N`): become N ranks, one per GPU
+        import subprocess
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.call(cmd))                          # a child process: this one never touches a GPU
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -450,7 +483,11 @@ def main():
         return bench_train(args, wl, dev, dist, rank, world)
     use_graph = not args.no_graph
     prec = args.precision
-    elapsed, info = run_sampler(dict(wl, read_sclk=(rank == 0 and not os.environ.get("PF_BENCH_NO_SCLK"))), K, W, dev, dist, rank, world, use_graph, prec)
+    full = args.full
+    elapsed, info = run_sampler(dict(wl, read_sclk=(full and rank == 0 and not os.environ.get("PF_BENCH_NO_SCLK"))), K, W, dev, dist, rank, world,
+                                use_graph, prec, time_kernels=full, full=full, want_final=bool(args.dump_outputs))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, info["final"])
     B, L = info["B"], info["L"]
     pairs = info["real_pairs"]                  # = B * L * L unless the batch is padded (cfg3): rooflines count unmasked pairs only
     split = 3 if prec == "fp32" else 1
@@ -459,46 +496,6 @@ def main():
     ms_per_step = elapsed / K * 1e3
     value = world * B * L * K / elapsed
     per_gpu = value / world
-    ku = info["kernel_us"]
-    et_s = ku["pf_edge_transition_fwd"]["avg_launch_us"] * 1e-6
-    ipa_s = ku["pf_ipa_attn_fwd"]["avg_launch_us"] * 1e-6
-    traffic, traffic_src, traffic_stale = pmc_traffic(args.workload, prec)
-    # which EdgeTransition kernel this plan launches: the hand-scheduled stream (v5) for the fp32-parity step with the pair tensor in
-    # fragment order, the 32x32 kernel (v4) for other fp32 forms, the 16x16x32 kernel (v3) in the f16 mode
-    et_kernel = (("edge_transition_v5h_kernel" if info.get("et_v5") else "edge_transition_v3_kernel") if prec != "fp32"
-                 else ("edge_transition_v5_kernel" if info.get("et_v5") else "edge_transition_v4_kernel"))
-    t_et = (traffic.get(et_kernel) or traffic.get("edge_transition_v4_kernel" if prec == "fp32" else "edge_transition_v3_kernel") or {}).get("hbm_bytes_corrected")
-    t_ipa = (traffic.get("ipa_two_kernel_form") or traffic.get("ipa_attn_kernel") or {}).get("hbm_bytes_corrected")
-    step_us = sum(v["us_per_step"] for v in ku.values())
-    share = {k: round(v["us_per_step"] / step_us, 3) for k, v in sorted(ku.items(), key=lambda kv: -kv[1]["us_per_step"])}
-    dominant = next(iter(share))
-    rf_et = {
-        "kernel": et_kernel + " (pf_edge_transition_fwd)", "bound": "mfma",
-        "achieved": pairs * ET_FLOPS_EXEC / et_s / 1e12, "peak": MFMA_F16_PEAK / split / 1e12, "unit": "TFLOP/s",
-        "frac": pairs * ET_FLOPS_EXEC * split / et_s / MFMA_F16_PEAK, "traffic": t_et,
-        "traffic_note": f"HBM bytes per launch from {traffic_src} (separate rocprofv3 --pmc passes); algorithmic = 512 B/pair = {pairs * ET_BYTES} B "
-                        "(+ 96 B/pair the kernel also writes for the NEXT attention block: 32 B pair bias + 64 B pair values, 32 as f16)",
-        "note": ("fp32-equivalent FLOPs; 3 f16 MFMA products per fp32 product (split precision), peak = 2.5 PF/3" if split == 3
-                 else "one f16 MFMA product per product, peak = 2.5 PF dense"),
-        "avg_launch_us": et_s * 1e6, "flops_per_pair_executed": ET_FLOPS_EXEC, "share_of_step": share.get("pf_edge_transition_fwd"),
-        "achieved_reference_flops": pairs * ET_FLOPS_REF / et_s / 1e12,
-        "hbm_achieved_GBps": pairs * ET_BYTES / et_s / 1e9,
-    }
-    cnt, cnt_src = pmc_counters(args.workload, prec, et_kernel)
-    if cnt is not None:
-        rf_et["mfma_busy"] = cnt["mfma_busy"]
-        rf_et["mfma_busy_note"] = (f"SQ_VALU_MFMA_BUSY_CYCLES / SIMD / launch cycles from {cnt_src} (recorded under rocprofv3, separate --pmc passes); "
-                                   f"waves parked {cnt['wave_cycles_parked']}, issue-stalled {cnt['wave_cycles_issue_stalled']} of their cycles, "
-                                   f"LDS bank conflicts {cnt['lds_bank_conflict_frac_of_lds_cycles']} of the LDS cycles")
-    rf_ipa = {
-        "kernel": "ipa attention (pf_ipa_attn_fwd)", "bound": "hbm",
-        "achieved": pairs * IPA_BYTES / ipa_s / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-        "frac": pairs * IPA_BYTES / ipa_s / HBM_PEAK, "traffic": t_ipa,
-        "traffic_note": f"HBM bytes per launch from {traffic_src}; algorithmic = 256 B/pair (one read of z, SURVEY.md 8(d)) = {pairs * IPA_BYTES} B; "
-                        "since round 2 (r02t) the pair aggregation reads the pair values W_dz z (64 B/pair, 32 in the f16 mode) that the EdgeTransition "
-                        "kernel emits instead of z itself, so the measured traffic lies BELOW the algorithmic figure",
-        "avg_launch_us": ipa_s * 1e6, "share_of_step": share.get("pf_ipa_attn_fwd"),
-    }
     out = {
         "metric": "residues x denoise-steps / s",
         "value": value, "unit": "res*step/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -507,54 +504,96 @@ def main():
         "config": {"workload": wl["name"], "per_gpu_batch": B, "residues": L, "global_batch": world * B,
                    "parallelism": f"batch-shard x{world}", "hipgraph": use_graph, "launches_per_step": info["launches_per_step"],
                    "precision": prec},
-        # dominant kernel of THIS workload first; the HBM-bound attention kernel beside it
-        "roofline": rf_et if dominant != "pf_ipa_attn_fwd" else rf_ipa,
-        "roofline_other": rf_ipa if dominant != "pf_ipa_attn_fwd" else rf_et,
-        "kernel_share_of_step": share,
-        # whole-step view against the HBM roofline of BASELINE.md section 4 (4096*L algorithmic bytes per residue-step)
-        # (fp32 pair tensor: 4096 B per unmasked PAIR and step = 16 passes over its 256 B of z; equals 4096 * L per residue-step for an
-        #  unpadded batch.  f16 mode with the pair tensor stored as f16 (engine.z16; the caller's fp32 edge embedding is converted
-        #  once per call): 16 passes over 128 B = 2048 B)
-        "hbm_roofline": {"bytes_per_pair_step": zb, "bytes_per_res_step": zb * L, "bytes_per_step": zb * pairs,
-                         "achieved_GBps": zb * pairs * K / elapsed / 1e9, "peak_GBps": HBM_PEAK / 1e9, "frac": zb * pairs * K / elapsed / HBM_PEAK,
-                         "pair_tensor": "f16" if zb != 4096 else "fp32"},
-        "final_state_check": info["validity"],
     }
-    if info.get("sclk") is not None:
-        out["clocks_under_load"] = info["sclk"]
-        mhz = (info["sclk"] or {}).get("sclk_mhz")
-        if mhz:
-            # the MFMA peak above is the part's figure at its 2.4 GHz boost clock; under this load the boxes hold less (one instantaneous
-            # read-out, +-10 % from read to read): the same achieved rate against the peak AT THE CLOCK THE BOX HELD
+    if full:
+        ku = info["kernel_us"]
+        et_s = ku["pf_edge_transition_fwd"]["avg_launch_us"] * 1e-6
+        ipa_s = ku["pf_ipa_attn_fwd"]["avg_launch_us"] * 1e-6
+        traffic, traffic_src, traffic_stale = pmc_traffic(args.workload, prec)
+        # which EdgeTransition kernel this plan launches: the hand-scheduled stream (v5) for the fp32-parity step with the pair tensor in
+        # fragment order, the 32x32 kernel (v4) for other fp32 forms, the 16x16x32 kernel (v3) in the f16 mode
+        et_kernel = (("edge_transition_v5h_kernel" if info.get("et_v5") else "edge_transition_v3_kernel") if prec != "fp32"
+                     else ("edge_transition_v5_kernel" if info.get("et_v5") else "edge_transition_v4_kernel"))
+        t_et = (traffic.get(et_kernel) or traffic.get("edge_transition_v4_kernel" if prec == "fp32" else "edge_transition_v3_kernel") or {}).get("hbm_bytes_corrected")
+        t_ipa = (traffic.get("ipa_two_kernel_form") or traffic.get("ipa_attn_kernel") or {}).get("hbm_bytes_corrected")
+        step_us = sum(v["us_per_step"] for v in ku.values())
+        share = {k: round(v["us_per_step"] / step_us, 3) for k, v in sorted(ku.items(), key=lambda kv: -kv[1]["us_per_step"])}
+        dominant = next(iter(share))
+        rf_et = {
+            "kernel": et_kernel + " (pf_edge_transition_fwd)", "bound": "mfma",
+            "achieved": pairs * ET_FLOPS_EXEC / et_s / 1e12, "peak": MFMA_F16_PEAK / split / 1e12, "unit": "TFLOP/s",
+            "frac": pairs * ET_FLOPS_EXEC * split / et_s / MFMA_F16_PEAK, "traffic": t_et,
+            "traffic_note": f"HBM bytes per launch from {traffic_src} (separate rocprofv3 --pmc passes); algorithmic = 512 B/pair = {pairs * ET_BYTES} B "
+                            "(+ 96 B/pair the kernel also writes for the NEXT attention block: 32 B pair bias + 64 B pair values, 32 as f16)",
+            "note": ("fp32-equivalent FLOPs; 3 f16 MFMA products per fp32 product (split precision), peak = 2.5 PF/3" if split == 3
+                     else "one f16 MFMA product per product, peak = 2.5 PF dense"),
+            "avg_launch_us": et_s * 1e6, "flops_per_pair_executed": ET_FLOPS_EXEC, "share_of_step": share.get("pf_edge_transition_fwd"),
+            "achieved_reference_flops": pairs * ET_FLOPS_REF / et_s / 1e12,
+            "hbm_achieved_GBps": pairs * ET_BYTES / et_s / 1e9,
+        }
+        cnt, cnt_src = pmc_counters(args.workload, prec, et_kernel)
+        if cnt is not None:
+            rf_et["mfma_busy"] = cnt["mfma_busy"]
+            rf_et["mfma_busy_note"] = (f"SQ_VALU_MFMA_BUSY_CYCLES / SIMD / launch cycles from {cnt_src} (recorded under rocprofv3, separate --pmc passes); "
+                                       f"waves parked {cnt['wave_cycles_parked']}, issue-stalled {cnt['wave_cycles_issue_stalled']} of their cycles, "
+                                       f"LDS bank conflicts {cnt['lds_bank_conflict_frac_of_lds_cycles']} of the LDS cycles")
+        rf_ipa = {
+            "kernel": "ipa attention (pf_ipa_attn_fwd)", "bound": "hbm",
+            "achieved": pairs * IPA_BYTES / ipa_s / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+            "frac": pairs * IPA_BYTES / ipa_s / HBM_PEAK, "traffic": t_ipa,
+            "traffic_note": f"HBM bytes per launch from {traffic_src}; algorithmic = 256 B/pair (one read of z, SURVEY.md 8(d)) = {pairs * IPA_BYTES} B; "
+                            "since round 2 (r02t) the pair aggregation reads the pair values W_dz z (64 B/pair, 32 in the f16 mode) that the EdgeTransition "
+                            "kernel emits instead of z itself, so the measured traffic lies BELOW the algorithmic figure",
+            "avg_launch_us": ipa_s * 1e6, "share_of_step": share.get("pf_ipa_attn_fwd"),
+        }
+        # dominant kernel of THIS workload first; the HBM-bound attention kernel beside it
+        out["roofline"] = rf_et if dominant != "pf_ipa_attn_fwd" else rf_ipa
+        out["roofline_other"] = rf_ipa if dominant != "pf_ipa_attn_fwd" else rf_et
+        out["kernel_share_of_step"] = share
+    # whole-step view against the HBM roofline of BASELINE.md section 4 (4096*L algorithmic bytes per residue-step)
+    # (fp32 pair tensor: 4096 B per unmasked PAIR and step = 16 passes over its 256 B of z; equals 4096 * L per residue-step for an
+    #  unpadded batch.  f16 mode with the pair tensor stored as f16 (engine.z16; the caller's fp32 edge embedding is converted
+    #  once per call): 16 passes over 128 B = 2048 B)
+    out["hbm_roofline"] = {"bytes_per_pair_step": zb, "bytes_per_res_step": zb * L, "bytes_per_step": zb * pairs,
+                          "achieved_GBps": zb * pairs * K / elapsed / 1e9, "peak_GBps": HBM_PEAK / 1e9, "frac": zb * pairs * K / elapsed / HBM_PEAK,
+                          "pair_tensor": "f16" if zb != 4096 else "fp32"}
+    if full:
+        out["final_state_check"] = info["validity"]
+        if info.get("sclk") is not None:
+            out["clocks_under_load"] = info["sclk"]
+            mhz = (info["sclk"] or {}).get("sclk_mhz")
+            if mhz:
+                # the MFMA peak above is the part's figure at its 2.4 GHz boost clock; under this load the boxes hold less (one instantaneous
+                # read-out, +-10 % from read to read): the same achieved rate against the peak AT THE CLOCK THE BOX HELD
+                for rf in (out["roofline"], out["roofline_other"]):
+                    if rf.get("bound") == "mfma":
+                        rf["frac_at_box_clock"] = rf["frac"] * 2400.0 / mhz
+                        rf["box_clock_note"] = f"peak scaled by sclk {mhz} MHz / 2400 MHz (rocm-smi read-out under load)"
+        sm = sustained_mfma()
+        if sm is not None:
+            # the same achieved rate against what a PURE MFMA stream sustains on this part (raw f16 products: 3 per fp32 product in the parity mode)
             for rf in (out["roofline"], out["roofline_other"]):
                 if rf.get("bound") == "mfma":
-                    rf["frac_at_box_clock"] = rf["frac"] * 2400.0 / mhz
-                    rf["box_clock_note"] = f"peak scaled by sclk {mhz} MHz / 2400 MHz (rocm-smi read-out under load)"
-    sm = sustained_mfma()
-    if sm is not None:
-        # the same achieved rate against what a PURE MFMA stream sustains on this part (raw f16 products: 3 per fp32 product in the parity mode)
+                    raw = rf["achieved"] * split
+                    rf["frac_of_sustained_mfma"] = [raw / sm[1], raw / sm[0]]
+                    rf["sustained_mfma_note"] = (f"raw f16 MFMA rate {raw:.0f} TFLOP/s against the {sm[0]:.0f} - {sm[1]:.0f} TFLOP/s a register-fed 32x32x16 f16 stream at 100 % "
+                                                 "matrix-pipe duty sustains on the whole chip for milliseconds (profiles/r06/mfma_power.txt, tools/dev/mfma_power.hip): "
+                                                 "`peak` is the 2.4 GHz boost figure, the chip holds 1.37 - 1.56 GHz under such a stream")
+        wst = whole_step_traffic(traffic, traffic_src, zb * pairs)
+        if wst is not None:
+            out["whole_step_traffic"] = wst
+        # The driver's record keeps `roofline` and `cpu_baseline` whole and only the NAMES of the other keys: the BASELINE headline
+        # fraction (whole-step HBM roofline), the counted / algorithmic traffic ratio, the clock the box held and whether the counted
+        # traffic belongs to the kernel sources that were timed ride inside `roofline` as well.
         for rf in (out["roofline"], out["roofline_other"]):
-            if rf.get("bound") == "mfma":
-                raw = rf["achieved"] * split
-                rf["frac_of_sustained_mfma"] = [raw / sm[1], raw / sm[0]]
-                rf["sustained_mfma_note"] = (f"raw f16 MFMA rate {raw:.0f} TFLOP/s against the {sm[0]:.0f} - {sm[1]:.0f} TFLOP/s a register-fed 32x32x16 f16 stream at 100 % "
-                                             "matrix-pipe duty sustains on the whole chip for milliseconds (profiles/r06/mfma_power.txt, tools/dev/mfma_power.hip): "
-                                             "`peak` is the 2.4 GHz boost figure, the chip holds 1.37 - 1.56 GHz under such a stream")
-    wst = whole_step_traffic(traffic, traffic_src, zb * pairs)
-    if wst is not None:
-        out["whole_step_traffic"] = wst
-    # The driver's record keeps `roofline` and `cpu_baseline` whole and only the NAMES of the other keys: the BASELINE headline
-    # fraction (whole-step HBM roofline), the counted / algorithmic traffic ratio, the clock the box held and whether the counted
-    # traffic belongs to the kernel sources that were timed ride inside `roofline` as well.
-    for rf in (out["roofline"], out["roofline_other"]):
-        rf["hbm_frac"] = out["hbm_roofline"]["frac"]
-        rf["hbm_frac_note"] = f"whole step: {zb} algorithmic B per pair and step x pairs / ms_per_step / 8 TB/s (BASELINE.json metric)"
-        rf["whole_step_traffic_ratio"] = wst["ratio"] if wst is not None else None
-        rf["sclk_mhz"] = (info.get("sclk") or {}).get("sclk_mhz")
-        rf["kernel_src_sha"] = kernel_src_sha()
-        rf["traffic_stale"] = traffic_stale
-        if traffic_stale:
-            rf["traffic_note"] = "STALE (recorded for other kernel sources than the ones timed here; tools/pmc_traffic.sh regenerates it) -- " + rf["traffic_note"]
+            rf["hbm_frac"] = out["hbm_roofline"]["frac"]
+            rf["hbm_frac_note"] = f"whole step: {zb} algorithmic B per pair and step x pairs / ms_per_step / 8 TB/s (BASELINE.json metric)"
+            rf["whole_step_traffic_ratio"] = wst["ratio"] if wst is not None else None
+            rf["sclk_mhz"] = (info.get("sclk") or {}).get("sclk_mhz")
+            rf["kernel_src_sha"] = kernel_src_sha()
+            rf["traffic_stale"] = traffic_stale
+            if traffic_stale:
+                rf["traffic_note"] = "STALE (recorded for other kernel sources than the ones timed here; tools/pmc_traffic.sh regenerates it) -- " + rf["traffic_note"]
     if ENGINE_OPTIONS:
         out["config"]["engine_options_forced"] = {k: int(v) for k, v in ENGINE_OPTIONS.items()}
     if info.get("buckets"):
@@ -574,45 +613,46 @@ def main():
                         "encode / bind_context / sampler_init / d2h once per sample() call")
     if comm is not None:
         out["rccl"] = comm
-    if world == 1 and not args.no_secondary and args.workload != "cfg2":
-        e2, i2 = run_sampler(WORKLOADS["cfg2"], K, W, dev, None, 0, 1, use_graph, prec, time_kernels=True)
-        k2 = i2["kernel_us"]
-        out["secondary"] = {"workload": WORKLOADS["cfg2"]["name"], "value": 16 * 64 * K / e2, "unit": "res*step/s",
-                            "ms_per_step": e2 / K * 1e3, "steps": K,
-                            "hbm_roofline_frac": 16 * 64 * K / e2 * 4096 * 64 / HBM_PEAK,
-                            "kernel_us_per_step": {k: round(v["us_per_step"], 1) for k, v in k2.items()}}
-    if world == 1 and not args.no_modes and args.workload == "cfg4" and prec == "fp32":
-        # the other configurations / precision modes BASELINE.json names, each timed the same way (K steps after W warm-up steps)
-        out["modes"] = {}
-        for name, wk, pm in (("f16@cfg4", "cfg4", "f16"), ("fp32@cfg3", "cfg3", "fp32"), ("f16@cfg3", "cfg3", "f16")):
-            em, im = run_sampler(WORKLOADS[wk], K, W, dev, None, 0, 1, use_graph, pm, time_kernels=False)
-            zbm = 2048 if im.get("z16") else 4096
-            ent = {"workload": WORKLOADS[wk]["name"], "precision": pm, "dtype": DTYPE[pm], "ms_per_step": em / K * 1e3,
-                   "value": im["B"] * im["L"] * K / em, "unit": "res*step/s", "steps": K, "residues": im["L"],
-                   "hbm_roofline_frac": zbm * im["real_pairs"] * K / em / HBM_PEAK, "bytes_per_pair_step": zbm,
-                   "final_state_check": im["validity"]}
-            if im.get("buckets"):
-                ent["length_buckets"] = im["buckets"]
-            if WORKLOADS[wk].get("variable"):
-                ent["value_real_residues"] = im["real_residues"] * K / em
-                ent["unmasked_pairs"] = im["real_pairs"]
-            out["modes"][name] = ent
-        # BASELINE configs[4] (train_ddp.py:117-156 per GPU): one graph-replayed training step, timed the same way (fewer steps: the
-        # step is ~4 x longer and the capture dominates the wall time of this entry)
-        try:
-            kt = max(10, K // 5)
-            tr = run_train(WORKLOADS["cfg5"], kt, 3, dev, None, 0, 1, use_graph)
-            out["modes"]["fp32@cfg5"] = {"workload": WORKLOADS["cfg5"]["name"], "precision": "fp32", "dtype": tr["dtype"], "ms_per_step": tr["ms_per_step"],
-                                         "value": tr["value"], "unit": tr["unit"], "steps": kt, "metric": tr["metric"],
-                                         "mfma_frac_of_split_ceiling": tr["roofline"]["frac"], "launches_per_step": tr["config"].get("launches_per_step")}
-        except Exception as e:                                   # the training entry must never take the inference line down with it
-            out["modes"]["fp32@cfg5"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if not os.environ.get("PF_BENCH_KEEP_CACHE"):
-            torch.cuda.empty_cache()
-    if world == 1 and not args.no_per_call and args.workload == "cfg4":
-        out["per_call"] = per_call_bench(dev, prec)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(info["sd"], info["batch"], B, L)
+    if full:
+        if world == 1 and not args.no_secondary and args.workload != "cfg2":
+            e2, i2 = run_sampler(WORKLOADS["cfg2"], K, W, dev, None, 0, 1, use_graph, prec, time_kernels=True)
+            k2 = i2["kernel_us"]
+            out["secondary"] = {"workload": WORKLOADS["cfg2"]["name"], "value": 16 * 64 * K / e2, "unit": "res*step/s",
+                                "ms_per_step": e2 / K * 1e3, "steps": K,
+                                "hbm_roofline_frac": 16 * 64 * K / e2 * 4096 * 64 / HBM_PEAK,
+                                "kernel_us_per_step": {k: round(v["us_per_step"], 1) for k, v in k2.items()}}
+        if world == 1 and not args.no_modes and args.workload == "cfg4" and prec == "fp32":
+            # the other configurations / precision modes BASELINE.json names, each timed the same way (K steps after W warm-up steps)
+            out["modes"] = {}
+            for name, wk, pm in (("f16@cfg4", "cfg4", "f16"), ("fp32@cfg3", "cfg3", "fp32"), ("f16@cfg3", "cfg3", "f16")):
+                em, im = run_sampler(WORKLOADS[wk], K, W, dev, None, 0, 1, use_graph, pm, time_kernels=False)
+                zbm = 2048 if im.get("z16") else 4096
+                ent = {"workload": WORKLOADS[wk]["name"], "precision": pm, "dtype": DTYPE[pm], "ms_per_step": em / K * 1e3,
+                       "value": im["B"] * im["L"] * K / em, "unit": "res*step/s", "steps": K, "residues": im["L"],
+                       "hbm_roofline_frac": zbm * im["real_pairs"] * K / em / HBM_PEAK, "bytes_per_pair_step": zbm,
+                       "final_state_check": im["validity"]}
+                if im.get("buckets"):
+                    ent["length_buckets"] = im["buckets"]
+                if WORKLOADS[wk].get("variable"):
+                    ent["value_real_residues"] = im["real_residues"] * K / em
+                    ent["unmasked_pairs"] = im["real_pairs"]
+                out["modes"][name] = ent
+            # BASELINE configs[4] (train_ddp.py:117-156 per GPU): one graph-replayed training step, timed the same way (fewer steps: the
+            # step is ~4 x longer and the capture dominates the wall time of this entry)
+            try:
+                kt = max(10, K // 5)
+                tr = run_train(WORKLOADS["cfg5"], kt, 3, dev, None, 0, 1, use_graph)
+                out["modes"]["fp32@cfg5"] = {"workload": WORKLOADS["cfg5"]["name"], "precision": "fp32", "dtype": tr["dtype"], "ms_per_step": tr["ms_per_step"],
+                                             "value": tr["value"], "unit": tr["unit"], "steps": kt, "metric": tr["metric"],
+                                             "mfma_frac_of_split_ceiling": tr["roofline"]["frac"], "launches_per_step": tr["config"].get("launches_per_step")}
+            except Exception as e:                                   # the training entry must never take the inference line down with it
+                out["modes"]["fp32@cfg5"] = {"error": f"{type(e).__name__}: {e}"[:300]}
+            if not os.environ.get("PF_BENCH_KEEP_CACHE"):
+                torch.cuda.empty_cache()
+        if world == 1 and not args.no_per_call and args.workload == "cfg4":
+            out["per_call"] = per_call_bench(dev, prec)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(info["sd"], info["batch"], B, L)
     if rank == 0:
         print(json.dumps(out))
     if dist is not None:
@@ -620,16 +660,20 @@ def main():
 
 
 def bench_train(args, wl, dev, dist, rank, world):
-    out = run_train(wl, args.steps, args.warmup, dev, dist, rank, world, not args.no_graph)
+    outputs = {} if args.dump_outputs else None
+    out = run_train(wl, args.steps, args.warmup, dev, dist, rank, world, not args.no_graph, outputs=outputs)
     if rank == 0:
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
 
 
-def run_train(wl, K, W, dev, dist, rank, world, use_graph):
+def run_train(wl, K, W, dev, dist, rank, world, use_graph, outputs=None):
     """cfg5: one training step = model(batch) -> weighted loss -> backward (HIP backward kernels) -> for N > 1 one flat
-    gradient all-reduce (RCCL).  Returns the JSON-able result line."""
+    gradient all-reduce (RCCL).  Returns the JSON-able result line.  outputs: a dict that receives the last step's six losses
+    and every parameter gradient ("grad.<parameter name>")."""
     import pepflowww_amd
     from pepflowww_amd import synth
     from pepflowww_amd.distributed import allreduce_gradients
@@ -651,13 +695,14 @@ def run_train(wl, K, W, dev, dist, rank, world, use_graph):
 
     def step():
         if graphed is not None:
-            graphed(None, noise=default_train_noise(B, L, gen), seed=20240227)
+            losses = graphed(None, noise=default_train_noise(B, L, gen), seed=20240227)
             graphed.allreduce(dist)                              # one all-reduce over the flat gradient buffer, in place
         else:
             model.zero_grad(set_to_none=True)
             losses = model(batch, noise=default_train_noise(B, L, gen), seed=20240227, first_sample=first)
             sum(wts[k] * v for k, v in losses.items()).backward()
             allreduce_gradients(model.parameters(), dist)
+        return losses
     for _ in range(W):
         step()
     torch.cuda.synchronize()
@@ -666,7 +711,7 @@ def run_train(wl, K, W, dev, dist, rank, world, use_graph):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(K):
-        step()
+        losses = step()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -678,6 +723,10 @@ def run_train(wl, K, W, dev, dist, rank, world, use_graph):
         elapsed = float(tt.item())
     grads = [p.grad for p in model.parameters() if p.grad is not None] if graphed is None else list(graphed.grads.values())
     assert grads and all(torch.isfinite(g).all() for g in grads), "non-finite gradients in the timed step"
+    if outputs is not None:
+        outputs.update({k: v.detach().cpu() for k, v in losses.items()})
+        named = graphed.grads.items() if graphed is not None else ((n, p.grad) for n, p in model.named_parameters() if p.grad is not None)
+        outputs.update({"grad." + n: g.detach().cpu() for n, g in named})
     grad_sync = None
     if dist is not None:
         # after the all-reduce every replica must hold the SAME averaged gradient: compare a float64 checksum across the ranks

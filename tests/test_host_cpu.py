@@ -374,6 +374,24 @@ def test_counted_traffic_is_flagged_when_recorded_for_other_kernel_sources(tmp_p
     assert bench.pmc_traffic("cfg4", "fp32")[2] is True
 
 
+def test_bench_dump_outputs_writes_float32_and_refuses_more_than_64_mb(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one DIR/<name>.npy per array, float32 whatever the tensor's dtype (sequence ids stay exact);
+    outputs beyond the size limit stop the run instead of writing a partial dump."""
+    import numpy as np
+    import bench
+    d = tmp_path / "out"
+    bench.dump_outputs(str(d), {"trans": torch.randn(2, 5, 3, dtype=torch.float64), "seqs": torch.arange(10).reshape(2, 5),
+                                "grad.w": torch.ones(4)})
+    assert sorted(os.listdir(d)) == ["grad.w.npy", "seqs.npy", "trans.npy"]
+    s = np.load(d / "seqs.npy")
+    assert s.dtype == np.float32 and s.shape == (2, 5) and np.array_equal(s, np.arange(10, dtype=np.float32).reshape(2, 5))
+    assert np.load(d / "trans.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 40)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(11)})
+    assert not (tmp_path / "big").exists()
+
+
 def test_torsion_angles_match_the_reference(golden_dir):
     """preprocess.get_torsion_angle vs golden F11 = the reference's models_con/torsion.py:48-65 on full-atom coordinates of every
     residue type (incl. UNK): psi and chi1-4 in [0, 2 pi) to 1e-5 rad (circular), the mask of defined angles exactly."""

@@ -2,7 +2,7 @@
 # dev-only: per-kernel average durations of one denoise step (graph off), all of our kernels  (run ON the GPU box)
 W=${1:-cfg2}; cd "$(dirname "$0")/../.." && export TMPDIR=/tmp
 OUT=gpurun_out/allk; rm -rf $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python bench.py --steps 20 --warmup 3 --no-graph --no-cpu-baseline --workload $W > $OUT.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python bench.py --full --steps 20 --warmup 3 --no-graph --no-cpu-baseline --workload $W > $OUT.log 2>&1
 f=$(find $OUT -name "*kernel_stats.csv" | head -1)
 python - "$f" <<'PY'
 import csv, sys

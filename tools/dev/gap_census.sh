@@ -4,7 +4,7 @@
 W=${1:-cfg4}; shift
 cd "$(dirname "$0")/../.." && export TMPDIR=/tmp
 OUT=gpurun_out/gap_$W; rm -rf $OUT
-PF_BENCH_NO_SCLK=1 rocprofv3 --kernel-trace --output-format csv -d $OUT -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --no-modes --no-per-call --workload $W "$@" > $OUT.log 2>&1
+PF_BENCH_NO_SCLK=1 rocprofv3 --kernel-trace --output-format csv -d $OUT -- python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --no-modes --no-per-call --workload $W "$@" > $OUT.log 2>&1
 f=$(find $OUT -name "*kernel_trace.csv" | head -1)
 python - "$f" <<'PY'
 import csv, sys, collections

@@ -1,29 +1,30 @@
 #!/bin/bash
 # HBM traffic of the big kernels (run ON the GPU box through gpurun): separate rocprofv3 --pmc passes for FETCH_SIZE and
-# WRITE_SIZE (only with --kernel-trace) -> gpurun_out/pmc_traffic_<tag>.json (copy to profiles/rNN/pmc_traffic.json)
+# WRITE_SIZE (only with --kernel-trace) -> $RES/pmc_traffic_<tag>.json (copy to profiles/rNN/pmc_traffic.json)
 TAG=${1:-r02}; COMMIT=${2:-unknown}; cd "$(dirname "$0")/.." && export TMPDIR=/tmp
+RES=${RES:-results}; mkdir -p $RES
 for W in cfg2 cfg4; do
   for P in fp32 f16; do
     [ $W = cfg2 ] && [ $P = f16 ] && continue
     for C in FETCH_SIZE WRITE_SIZE; do
-      OUT=gpurun_out/pt_${W}_${P}_$C; rm -rf $OUT
-      PF_BENCH_NO_SCLK=1 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT -- python bench.py --steps 4 --warmup 1 --no-graph --no-cpu-baseline --no-secondary --no-modes --no-per-call --workload $W --precision $P > $OUT.log 2>&1
+      OUT=$RES/pt_${W}_${P}_$C; rm -rf $OUT
+      PF_BENCH_NO_SCLK=1 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT -- python bench.py --full --steps 4 --warmup 1 --no-graph --no-cpu-baseline --no-secondary --no-modes --no-per-call --workload $W --precision $P > $OUT.log 2>&1
     done
   done
 done
-python - "$TAG" "$COMMIT" <<'PY'
+python - "$TAG" "$COMMIT" "$RES" <<'PY'
 import csv, glob, json, re, sys, collections
-tag, commit = sys.argv[1], sys.argv[2]
+tag, commit, res_dir = sys.argv[1], sys.argv[2], sys.argv[3]
 sys.path.insert(0, ".")
 import bench
 res = {"_commit": commit, "_src_sha": bench.kernel_src_sha(),
-       "_how": "rocprofv3 --pmc FETCH_SIZE (resp. WRITE_SIZE, separate pass) --kernel-trace --output-format csv -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --no-graph --workload W --precision P; per-kernel average of Counter_Value (KiB). Correction per MI355X_MICROARCH.md (HBM): FETCH_SIZE counts 128-B requests as 64 B for wide coalesced 16 B/lane reads -> doubled; WRITE_SIZE as reported."}
+       "_how": "rocprofv3 --pmc FETCH_SIZE (resp. WRITE_SIZE, separate pass) --kernel-trace --output-format csv -- python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --no-graph --workload W --precision P; per-kernel average of Counter_Value (KiB). Correction per MI355X_MICROARCH.md (HBM): FETCH_SIZE counts 128-B requests as 64 B for wide coalesced 16 B/lane reads -> doubled; WRITE_SIZE as reported."}
 KEYS = ("edge_transition_v5h_kernel", "edge_transition_v5_kernel", "edge_transition_v4_kernel", "edge_transition_v3_kernel", "edge_transition_kernel", "ipa_attn_kernel", "ipa_scores_kernel", "ipa_scores16_kernel", "ipa_pair_kernel", "ipa_pair_dz_kernel", "ipa_pair_dz16_kernel", "linear_split_kernel", "linear_rows_kernel", "node_tfmr_kernel", "node_head_kernel", "node_head32_kernel")
 for W in ("cfg2", "cfg4"):
     for P in ("fp32", "f16"):
         acc = collections.defaultdict(lambda: collections.defaultdict(list))
         for C in ("FETCH_SIZE", "WRITE_SIZE"):
-            for f in glob.glob(f"gpurun_out/pt_{W}_{P}_{C}/**/*counter_collection.csv", recursive=True):
+            for f in glob.glob(f"{res_dir}/pt_{W}_{P}_{C}/**/*counter_collection.csv", recursive=True):
                 for row in csv.DictReader(open(f)):
                     k = row["Kernel_Name"]
                     for key in KEYS:
@@ -42,7 +43,7 @@ for W in ("cfg2", "cfg4"):
         # The run holds W + K sampler steps + min(K, 10) instrumented plan runs = 1 + 4 + 4 = 9 passes over the plan.
         allk = collections.defaultdict(lambda: collections.defaultdict(list))
         for C in ("FETCH_SIZE", "WRITE_SIZE"):
-            for f in glob.glob(f"gpurun_out/pt_{W}_{P}_{C}/**/*counter_collection.csv", recursive=True):
+            for f in glob.glob(f"{res_dir}/pt_{W}_{P}_{C}/**/*counter_collection.csv", recursive=True):
                 for row in csv.DictReader(open(f)):
                     k = row["Kernel_Name"]
                     if "anonymous namespace" in k and "at::" not in k and "rocprim" not in k and row["Counter_Name"] == C and "edge_features" not in k and "node_features" not in k:
@@ -64,7 +65,7 @@ for W in ("cfg2", "cfg4"):
         if sk in res[name] and pk in res[name]:
             a, b = res[name][sk], res[name][pk]
             res[name]["ipa_two_kernel_form"] = {"hbm_bytes_corrected": a["hbm_bytes_corrected"] + b["hbm_bytes_corrected"], "note": sk + " + " + pk + " (one pf_ipa_attn_fwd call)"}
-json.dump(res, open(f"gpurun_out/pmc_traffic_{tag}.json", "w"), indent=1)
+json.dump(res, open(f"{res_dir}/pmc_traffic_{tag}.json", "w"), indent=1)
 print(json.dumps(res, indent=1))
 PY
-rm -rf gpurun_out/pt_cfg*
+rm -rf $RES/pt_cfg*
