@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PF_ABI_VERSION 59
+#define PF_ABI_VERSION 60
 #define PF_ATT_VROWS 164             /* rows of a head's transposed value block: 128 channels + 12 points x 3 */
 /* att_vt (f16 mode, ABI 53): a head's transposed values [PF_ATT_VROWS rows][keys] in the FRAGMENT ORDER of the score kernel's second
  * product -- block (tile n, 32-key step) = 512 f16 = the eight operand slots of each of its 64 lanes: row c sits in tile n = c & 7 as
@@ -781,6 +781,54 @@ typedef struct {
     int B, L;
 } pf_backbone_atoms_args;
 int pf_backbone_atoms_fwd(const pf_backbone_atoms_args* a, pf_stream_t stream);
+
+/* ---- evaluation of sampled peptides (ABI 60) ------------------------------------------------------------------------------
+ * pf_superpose_fwd: superposition of point sets over a work list, one wave per pair, one launch.  Pair p = (i, j) = pairs[2p],
+ * pairs[2p+1] uses the points n with mx[i,n] & my[j,n].  The points are centred first; the cross terms S = X^T Y and the squared
+ * norms are accumulated in fp64 and the 3x3 SVD (one-sided Jacobi) runs in fp64.
+ *   rmsd_plain[p]  RMSD without superposition;
+ *   rmsd[p]        minimal RMSD over proper rotations + translation (Kabsch with reflection correction: Biopython's
+ *                  Superimposer.rms), E_x + E_y - 2 (s1 + s2 + sign(det S) s3) clamped at 0;
+ *   count[p]       points used; 0 -> every float output of the pair is NaN;
+ *   ident[p]       fraction of those points with aa_x[i,n] == aa_y[j,n] (optional, needs aa_x / aa_y);
+ *   rot[p] 3x3 row-major, trans[p] 3: y ~ rot x + trans in the mode `allow_reflection` (optional, both or neither):
+ *                  1 = r = V U^T from S = U Sigma V^T without determinant correction (pepflow/modules/common/geometry.py:18-56
+ *                  align / batch_align), 0 = the proper Kabsch rotation;
+ *   aligned[p]     rot x[i,n] + trans for ALL n, masked points included ([P,N,3], optional, needs no rot / trans buffers);
+ *   degenerate[p]  1 where S has numerical rank < 2 (s2 <= 1e-6 s1): the rotation is not unique, the identity is returned
+ *                  (the RMSDs stay exact); optional.
+ * Pair indices outside [0, Bx) x [0, By) are treated as count = 0.  y may alias x. */
+typedef struct {
+    const float* x; const float* y;                     /* [Bx,N,3], [By,N,3] */
+    const unsigned char* mx; const unsigned char* my;   /* [Bx,N], [By,N] */
+    const int64_t* aa_x; const int64_t* aa_y;           /* [Bx,N], [By,N] (optional, both or neither) */
+    const int* pairs;                                   /* [P,2] */
+    float* rmsd_plain; float* rmsd; int* count;         /* [P] */
+    float* ident;                                       /* [P] optional */
+    float* rot; float* trans;                           /* [P,9], [P,3] optional */
+    float* aligned;                                     /* [P,N,3] optional */
+    unsigned char* degenerate;                          /* [P] optional */
+    int Bx, By, N, P;
+    int allow_reflection;
+} pf_superpose_args;
+int pf_superpose_fwd(const pf_superpose_args* a, pf_stream_t stream);
+
+/* pf_binding_site_fwd: binding-site contacts of eval/geometry.py:93-110 (get_bind_site / get_bind_ratio) on CA coordinates.  For
+ * every sample b, the context residues r (res_mask & !gen_mask & ctx_atom_mask[b,r,ca_atom]) with some generated residue p
+ * (gen_mask & res_mask) at |ctx_pos[b,r,ca_atom] - pep[b,p]| <= cutoff are marked, once for pep_sample (the sampled CA) and once
+ * for pep_native; bsr[b] = |site_sample & site_native| / (|site_native| + 1e-10).  One block per sample. */
+typedef struct {
+    const float* ctx_pos;                     /* [B,L,n_atoms,3] heavy atoms of the complex */
+    const unsigned char* ctx_atom_mask;       /* [B,L,n_atoms] */
+    int n_atoms, ca_atom;
+    const unsigned char* res_mask; const unsigned char* gen_mask;   /* [B,L] */
+    const float* pep_sample; const float* pep_native;               /* [B,L,3] */
+    float cutoff;
+    unsigned char* site_sample; unsigned char* site_native;         /* [B,L] */
+    float* bsr;                                                     /* [B] */
+    int B, L;
+} pf_binding_site_args;
+int pf_binding_site_fwd(const pf_binding_site_args* a, pf_stream_t stream);
 
 #ifdef __cplusplus
 }

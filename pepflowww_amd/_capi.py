@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (PF_LIB_PATH: another build of the same library -- same-box A/B runs of kernel variants, tools/dev)
 LIB_PATH = os.environ.get("PF_LIB_PATH") or os.path.join(_HERE, "lib", "libpepflow_hip.so")
-ABI_VERSION = 59
+ABI_VERSION = 60
 
 _fp = C.c_void_p
 _i = C.c_int
@@ -167,6 +167,18 @@ class NodeTfmrArgs(C.Structure):
                 ("h_w", (_fp * 3) * 2), ("h_b", (_fp * 3) * 2), ("logits_out", _fp), ("ang_out", _fp), ("single_pass", _i), ("key_end", _fp), ("dump", _fp * 11), ("row_on", _fp)]
 
 
+class SuperposeArgs(C.Structure):
+    _fields_ = [("x", _fp), ("y", _fp), ("mx", _fp), ("my", _fp), ("aa_x", _fp), ("aa_y", _fp), ("pairs", _fp),
+                ("rmsd_plain", _fp), ("rmsd", _fp), ("count", _fp), ("ident", _fp), ("rot", _fp), ("trans", _fp), ("aligned", _fp),
+                ("degenerate", _fp), ("Bx", _i), ("By", _i), ("N", _i), ("P", _i), ("allow_reflection", _i)]
+
+
+class BindingSiteArgs(C.Structure):
+    _fields_ = [("ctx_pos", _fp), ("ctx_atom_mask", _fp), ("n_atoms", _i), ("ca_atom", _i), ("res_mask", _fp), ("gen_mask", _fp),
+                ("pep_sample", _fp), ("pep_native", _fp), ("cutoff", C.c_float), ("site_sample", _fp), ("site_native", _fp),
+                ("bsr", _fp), ("B", _i), ("L", _i)]
+
+
 class EtBwdArgs(C.Structure):
     _fields_ = [("g_y", _fp), ("h1", _fp), ("h2", _fp), ("wfT_f16", _fp), ("w2T_f16", _fp), ("w1T_f16", _fp),
                 ("g_h2", _fp), ("g_h1", _fp), ("g_x", _fp), ("npairs", C.c_longlong), ("m1", _fp), ("m2", _fp)]
@@ -240,6 +252,8 @@ _SIGNATURES = {
     "pf_so3_log": ([_fp, _fp, _i, _fp], _i),
     "pf_so3_exp": ([_fp, _fp, _i, _fp], _i),
     "pf_torus_geodesic": ([_fp, _fp, _fp, _fp, _i, _fp], _i),
+    "pf_superpose_fwd": ([C.POINTER(SuperposeArgs), _fp], _i),
+    "pf_binding_site_fwd": ([C.POINTER(BindingSiteArgs), _fp], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

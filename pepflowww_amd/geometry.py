@@ -1,0 +1,119 @@
+"""Superposition on the device: drop-in for `align` / `batch_align` of pepflow/modules/common/geometry.py:18-56 (imported by the
+reference's sampling drivers), Kabsch RMSD and the pairwise RMSD / sequence-identity matrix of a set of samples, on the HIP kernel
+pf_superpose_fwd (one wave per pair of a work list, fp64 sums and 3x3 SVD).
+
+Deviation from the reference: `batch_align` selects each sample's masked atoms on their own.  The reference's
+`masked_select(...).reshape(B, -1, 3)` mixes atoms across samples when the per-sample mask counts differ; where the counts are equal
+the results are the same."""
+import ctypes as C
+
+import torch
+
+from . import _capi
+
+
+def _f32(t, shape, dev):
+    return t.to(dev, torch.float32).reshape(shape).contiguous()
+
+
+def _u8(t, shape, dev):
+    return t.to(dev).to(torch.uint8).reshape(shape).contiguous()
+
+
+def superpose(x, y, mx, my, pairs, aa_x=None, aa_y=None, allow_reflection=False, transform=False, aligned=False):
+    """pf_superpose_fwd over the work list `pairs` [P,2] (pair p = (i, j): x[i] onto y[j] on the points mx[i] & my[j]).
+
+    x [Bx,N,3], y [By,N,3] (y may be x), mx [Bx,N], my [By,N], aa_x / aa_y [B.,N] int64 (optional, both or neither).
+    -> dict of device tensors: rmsd_plain, rmsd (proper Kabsch), count, degenerate [P]; ident [P] if aa_x is given; rot [P,3,3],
+    trans [P,3] if `transform`; aligned [P,N,3] (rot x[i] + trans for all N points) if `aligned`.  rot / trans / aligned follow
+    `allow_reflection` (True: the reference's `align` rotation, which may be a reflection; False: the proper rotation)."""
+    dev = x.device
+    Bx, N, _ = x.shape
+    By = y.shape[0]
+    if y.shape[1:] != (N, 3) or tuple(mx.shape) != (Bx, N) or tuple(my.shape) != (By, N):
+        raise ValueError(f"shapes do not agree: x {tuple(x.shape)}, y {tuple(y.shape)}, mx {tuple(mx.shape)}, my {tuple(my.shape)}")
+    if (aa_x is None) != (aa_y is None):
+        raise ValueError("aa_x and aa_y go together")
+    keep = [_f32(x, (Bx, N, 3), dev)]
+    keep.append(keep[0] if y is x else _f32(y, (By, N, 3), dev))
+    keep += [_u8(mx, (Bx, N), dev)]
+    keep.append(keep[2] if my is mx else _u8(my, (By, N), dev))
+    pairs = pairs.to(dev, torch.int32).reshape(-1, 2).contiguous()
+    P = pairs.shape[0]
+    a = _capi.SuperposeArgs()
+    a.x, a.y, a.mx, a.my = (_capi.dptr(t, t.dtype, nm) for t, nm in zip(keep, ("x", "y", "mx", "my")))
+    a.pairs = _capi.dptr(pairs, torch.int32, "pairs")
+    out = {"rmsd_plain": torch.empty(P, device=dev), "rmsd": torch.empty(P, device=dev),
+           "count": torch.empty(P, dtype=torch.int32, device=dev), "degenerate": torch.empty(P, dtype=torch.uint8, device=dev)}
+    if aa_x is not None:
+        keep.append(aa_x.to(dev, torch.int64).reshape(Bx, N).contiguous())
+        keep.append(keep[-1] if aa_y is aa_x else aa_y.to(dev, torch.int64).reshape(By, N).contiguous())
+        a.aa_x, a.aa_y = keep[-2].data_ptr(), keep[-1].data_ptr()
+        out["ident"] = torch.empty(P, device=dev)
+    if transform:
+        out["rot"], out["trans"] = torch.empty(P, 3, 3, device=dev), torch.empty(P, 3, device=dev)
+    if aligned:
+        out["aligned"] = torch.empty(P, N, 3, device=dev)
+    for k in ("rmsd_plain", "rmsd", "count", "degenerate", "ident", "rot", "trans", "aligned"):
+        if k in out:
+            setattr(a, k, out[k].data_ptr())
+    a.Bx, a.By, a.N, a.P, a.allow_reflection = Bx, By, N, P, int(bool(allow_reflection))
+    if P:
+        _capi.check(_capi.load().pf_superpose_fwd(C.byref(a), _capi.stream_ptr()), "pf_superpose_fwd")
+    out["degenerate"] = out["degenerate"].bool()
+    return out
+
+
+def batch_align(pos_1, pos_2, pos_mask):
+    """(B,L,A,3), (B,L,A,3), (B,L,A) -> (pos_1 aligned onto pos_2, pos_2).  The reference's rule: r = V U^T from the SVD of
+    S = X^T Y over the masked atoms (no determinant correction: a mirror image is aligned by a reflection), applied with its
+    translation to every atom of pos_1, masked ones included."""
+    B, L, A, _ = pos_1.shape
+    ids = torch.arange(B, device=pos_1.device, dtype=torch.int32)
+    out = superpose(pos_1.reshape(B, L * A, 3), pos_2.reshape(B, L * A, 3), pos_mask.reshape(B, L * A), pos_mask.reshape(B, L * A),
+                    torch.stack([ids, ids], 1), allow_reflection=True, aligned=True)
+    return out["aligned"].reshape(B, L, A, 3).to(pos_1.dtype), pos_2
+
+
+def align(pos_1, pos_2, pos_mask):
+    """(L,A,3), (L,A,3), (L,A) -> (pos_1 aligned onto pos_2, pos_2): `batch_align` of one sample."""
+    aligned, _ = batch_align(pos_1[None], pos_2[None], pos_mask[None])
+    return aligned[0], pos_2
+
+
+def superpose_rmsd(x, y, mask):
+    """x, y [B,N,3], mask [B,N] -> [B]: RMSD after the optimal proper rotation and translation of x[b] onto y[b] (Kabsch;
+    Biopython's Superimposer.rms).  NaN where the mask is empty."""
+    ids = torch.arange(x.shape[0], device=x.device, dtype=torch.int32)
+    return superpose(x, y, mask, mask, torch.stack([ids, ids], 1))["rmsd"]
+
+
+def group_pairs(groups):
+    """groups [B] (any integer labels) -> (pairs [P,2] int32 of every i < j with the same label, group index [P] into `labels`,
+    labels [G] sorted).  Index plumbing on the host."""
+    groups = torch.as_tensor(groups).reshape(-1).cpu()
+    labels, inv = torch.unique(groups, sorted=True, return_inverse=True)
+    i, j = torch.triu_indices(groups.numel(), groups.numel(), offset=1)
+    same = inv[i] == inv[j]
+    pairs = torch.stack([i[same], j[same]], 1).to(torch.int32)
+    return pairs, inv[i[same]], labels
+
+
+def pairwise_superpose_rmsd(x, mask, aa=None, groups=None):
+    """x [B,N,3], mask [B,N] -> rmsd [B,B]: proper Kabsch RMSD of every pair i < j of the same group (all one group when `groups`
+    is None), mirrored, so the matrix is exactly symmetric with an exact-zero diagonal; pairs across groups are NaN.
+    With `aa` [B,N] -> (rmsd, ident [B,B]): the fraction of the shared points with the same residue type (diagonal 1)."""
+    B = x.shape[0]
+    dev = x.device
+    pairs, _, _ = group_pairs(torch.zeros(B, dtype=torch.int64) if groups is None else groups)
+    out = superpose(x, x, mask, mask, pairs, aa_x=aa, aa_y=aa)
+    i, j = pairs[:, 0].to(dev, torch.int64), pairs[:, 1].to(dev, torch.int64)
+    eye = torch.eye(B, dtype=torch.bool, device=dev)
+
+    def mirror(v, diag):
+        m = torch.full((B, B), float("nan"), device=dev)
+        m[i, j] = v
+        m[j, i] = v
+        return m.masked_fill(eye, diag)
+    rmsd = mirror(out["rmsd"], 0.0)
+    return rmsd if aa is None else (rmsd, mirror(out["ident"], 1.0))

@@ -1,0 +1,111 @@
+"""Quality metrics of sampled peptides on the device: what the reference's sampling driver reports after `sample()`
+(models_con/inference.py:77-79: CA RMSD, rotation RMSD, amino-acid recovery) and what its evaluation adds (eval/geometry.py:
+CA RMSD after superposition, `get_rmsd` 47-59; binding-site ratio, `get_bind_site` / `get_bind_ratio` 93-110; diversity among the
+samples of one complex), without Biopython / tmtools / mdtraj and without writing PDB files.
+
+Every per-residue and per-point operation runs in pf_superpose_fwd / pf_binding_site_fwd; the host builds pair lists and masks and
+combines per-sample (or per-pair) outputs."""
+import ctypes as C
+import math
+
+import torch
+
+from . import _capi
+from .geometry import group_pairs, superpose
+
+BIND_CUTOFF = 10.0          # eval/geometry.py:100: receptor residues within 10 A of a peptide CA
+CA_ATOM = 1                 # BBHeavyAtom.CA
+
+
+def _check_groups(gen, groups):
+    """-> group labels [B] (CPU int64).  The samples of one group must share the generate mask (one complex, replicated)."""
+    B = gen.shape[0]
+    g = torch.zeros(B, dtype=torch.int64) if groups is None else torch.as_tensor(groups).reshape(-1).cpu().to(torch.int64)
+    if g.numel() != B:
+        raise ValueError(f"groups has {g.numel()} labels for {B} samples")
+    gen = gen.cpu().bool()
+    for lab in torch.unique(g):
+        rows = gen[g == lab]
+        if not bool((rows == rows[0]).all()):
+            raise ValueError("samples of one group must have the same generate_mask"
+                             + (" (groups=None treats the batch as one complex; pass groups for a batch of several)" if groups is None else ""))
+    return g
+
+
+def _device(*ts):
+    for t in ts:
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def binding_site(ctx_pos, ctx_atom_mask, res_mask, gen_mask, pep_sample, pep_native, cutoff=BIND_CUTOFF, ca_atom=CA_ATOM):
+    """pf_binding_site_fwd -> (site_sample [B,L] bool, site_native [B,L] bool, bsr [B])."""
+    B, L, A, _ = ctx_pos.shape
+    dev = _device(ctx_pos, pep_sample, res_mask)
+    keep = [ctx_pos.to(dev, torch.float32).contiguous(), ctx_atom_mask.to(dev).to(torch.uint8).contiguous(),
+            res_mask.to(dev).to(torch.uint8).contiguous(), gen_mask.to(dev).to(torch.uint8).contiguous(),
+            pep_sample.to(dev, torch.float32).reshape(B, L, 3).contiguous(), pep_native.to(dev, torch.float32).reshape(B, L, 3).contiguous()]
+    s_site, n_site = torch.empty(B, L, dtype=torch.uint8, device=dev), torch.empty(B, L, dtype=torch.uint8, device=dev)
+    bsr = torch.empty(B, device=dev)
+    a = _capi.BindingSiteArgs()
+    a.ctx_pos, a.ctx_atom_mask, a.res_mask, a.gen_mask, a.pep_sample, a.pep_native = (
+        _capi.dptr(t, t.dtype, "binding_site input") for t in keep)
+    a.n_atoms, a.ca_atom, a.cutoff, a.B, a.L = A, ca_atom, float(cutoff), B, L
+    a.site_sample, a.site_native, a.bsr = s_site.data_ptr(), n_site.data_ptr(), bsr.data_ptr()
+    _capi.check(_capi.load().pf_binding_site_fwd(C.byref(a), _capi.stream_ptr()), "pf_binding_site_fwd")
+    return s_site.bool(), n_site.bool(), bsr
+
+
+def evaluate_samples(final, batch, groups=None):
+    """final: traj[-1] of FlowModel.sample (keys rotmats, trans, seqs, rotmats_1, trans_1, seqs_1; CPU or device tensors);
+    batch: generate_mask, res_mask, pos_heavyatom, mask_heavyatom.  groups [B]: the complex of each sample (None: one complex,
+    which needs the same generate_mask in every sample; ValueError otherwise).
+
+    -> dict of device tensors.  Per sample [B], over the generated residues:
+      ca_rmsd          RMSD of trans against trans_1, no superposition;
+      ca_rmsd_aligned  the same after the optimal proper superposition (get_rmsd's second value);
+      rot_rmsd         sqrt(sum ||R - R_1||_F^2 / n): sqrt(3) x the plain RMSD of the matrix rows taken as three points per residue;
+      aar              fraction of seqs equal to seqs_1;
+      bsr              binding-site ratio: receptor residues within 10 A of a sampled peptide CA that are also within 10 A of a
+                       native one, over the latter (+1e-10);
+      count            generated residues; site_sample / site_native [B,L] the two binding sites.
+    Pooled over the batch (float64 scalars), inference.py:77-79 with their +1e-8: ca_rmsd_pooled, rot_rmsd_pooled, aar_pooled.
+    Per group [G] (labels in group_labels): diversity_rmsd = mean aligned CA RMSD over the pairs i < j, diversity_seq = 1 - their
+    mean sequence identity (NaN for a group of one)."""
+    gen_cpu = batch["generate_mask"]
+    labels = _check_groups(gen_cpu, groups)
+    dev = _device(batch["generate_mask"], final["trans"], batch["pos_heavyatom"])
+    final = {k: final[k].to(dev) for k in ("rotmats", "trans", "seqs", "rotmats_1", "trans_1", "seqs_1")}
+    B, L = final["seqs"].shape
+    gen = batch["generate_mask"].to(dev).bool()
+    ids = torch.arange(B, dtype=torch.int32)
+    diag = torch.stack([ids, ids], 1)
+
+    ca = superpose(final["trans"], final["trans_1"], gen, gen, diag, aa_x=final["seqs"], aa_y=final["seqs_1"])
+    gen3 = gen[:, :, None].expand(B, L, 3).reshape(B, 3 * L)
+    # ||R - R_1||_F^2 is the summed squared distance of the three rows (equally: the three columns) taken as points
+    rot = superpose(final["rotmats"].reshape(B, 3 * L, 3), final["rotmats_1"].reshape(B, 3 * L, 3), gen3, gen3, diag)
+
+    pairs, gidx, glab = group_pairs(labels)
+    div = superpose(final["trans"], final["trans"], gen, gen, pairs, aa_x=final["seqs"], aa_y=final["seqs"])
+    G = glab.numel()
+    gidx = gidx.to(dev)
+    npair = torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, torch.ones_like(gidx, dtype=torch.float64))
+    div_rmsd = torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, div["rmsd"].double()) / npair
+    div_seq = 1.0 - torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, div["ident"].double()) / npair
+
+    s_site, n_site, bsr = binding_site(batch["pos_heavyatom"], batch["mask_heavyatom"], batch["res_mask"], gen, final["trans"],
+                                       final["trans_1"])
+
+    n = ca["count"].double()
+    rot_rmsd = rot["rmsd_plain"] * math.sqrt(3.0)
+    tot = n.sum() + 1e-8
+    # per-sample sums back from the per-sample means (samples without generated residues contribute nothing)
+    ca_sum = torch.nan_to_num(ca["rmsd_plain"].double() ** 2 * n).sum()
+    rot_sum = torch.nan_to_num(rot["rmsd_plain"].double() ** 2 * 3.0 * n).sum()
+    same = torch.nan_to_num(torch.round(ca["ident"].double() * n)).sum()
+    return {"ca_rmsd": ca["rmsd_plain"], "ca_rmsd_aligned": ca["rmsd"], "rot_rmsd": rot_rmsd, "aar": ca["ident"], "bsr": bsr,
+            "count": ca["count"], "site_sample": s_site, "site_native": n_site,
+            "ca_rmsd_pooled": torch.sqrt(ca_sum / tot), "rot_rmsd_pooled": torch.sqrt(rot_sum / tot), "aar_pooled": same / tot,
+            "diversity_rmsd": div_rmsd, "diversity_seq": div_seq, "group_labels": glab.to(dev)}

@@ -1,0 +1,121 @@
+"""Times the evaluation kernels against the same work done with torch ops and torch.linalg.svd on the device.
+
+Cases: the pairwise superposition at 64 samples x 25 CA (2 016 pairs), the same at 16 groups x 64 samples (32 256 pairs), and
+batch_align at B = 64, L = 128, A = 15.  Per case: `call` = device events around REPS back-to-back calls of the Python function
+(host overhead included), `graph` = the same calls captured once as a graph and replayed (device time per call; HIP only).  Prints one JSON
+line.  Usage: python tools/eval_bench.py [--reps 200]"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pepflowww_amd import _capi, geometry, synth  # noqa: E402
+
+
+def torch_pairwise(x, m, pairs):
+    """proper Kabsch RMSD of the pairs (i, j) on mx[i] & mx[j], torch ops + batched torch.linalg.svd"""
+    i, j = pairs[:, 0].long(), pairs[:, 1].long()
+    a, b = x[i], x[j]
+    w = (m[i] & m[j]).float()[..., None]
+    n = w.sum(1, keepdim=True)
+    a = a - (a * w).sum(1, keepdim=True) / n
+    b = b - (b * w).sum(1, keepdim=True) / n
+    s = (a * w).transpose(1, 2) @ b
+    u, sig, vt = torch.linalg.svd(s)
+    d = torch.sign(torch.linalg.det(u) * torch.linalg.det(vt))
+    lam = sig[:, 0] + sig[:, 1] + d * sig[:, 2]
+    e = ((a * a * w).sum((1, 2)) + (b * b * w).sum((1, 2)) - 2 * lam).clamp_min(0)
+    return torch.sqrt(e / n[:, 0, 0])
+
+
+def torch_batch_align(p1, p2, mask):
+    """the reference's rule r = V U^T per sample (masked atoms as weights), applied to every atom"""
+    B = p1.shape[0]
+    x, y, w = p1.reshape(B, -1, 3), p2.reshape(B, -1, 3), mask.reshape(B, -1, 1).float()
+    n = w.sum(1, keepdim=True)
+    xm, ym = (x * w).sum(1, keepdim=True) / n, (y * w).sum(1, keepdim=True) / n
+    s = ((x - xm) * w).transpose(1, 2) @ (y - ym)
+    u, _, vt = torch.linalg.svd(s)
+    r = vt.transpose(1, 2) @ u.transpose(1, 2)
+    t = ym - xm @ r.transpose(1, 2)
+    return (x @ r.transpose(1, 2) + t).reshape(p1.shape)
+
+
+def timed(fn, reps, graph=True):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    call = e0.elapsed_time(e1) * 1e3 / reps
+    if not graph:                      # (torch.linalg.svd is not captured: its solver may synchronise with the host)
+        return {"call_us": round(call, 2)}
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(s):
+        fn()
+        torch.cuda.synchronize()
+        with _capi.capture_guard(), torch.cuda.graph(g, stream=s):
+            for _ in range(reps):
+                fn()
+    torch.cuda.synchronize()
+    g.replay()
+    torch.cuda.synchronize()
+    e0.record()
+    g.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return {"call_us": round(call, 2), "graph_us": round(e0.elapsed_time(e1) * 1e3 / reps, 2)}
+
+
+def pocket_cas(n_complex, n_samples, seed):
+    """n_complex x n_samples peptide CA sets of 25 residues (samples of one complex: the native plus 2 A noise)"""
+    xs = []
+    for c in range(n_complex):
+        batch = synth.make_pocket_batch(1, 60, 25, seed=seed + c)
+        ca = batch["pos_heavyatom"][0, batch["generate_mask"][0], 1]
+        g = torch.Generator().manual_seed(seed + c)
+        xs.append(ca[None] + 2.0 * torch.randn(n_samples, 25, 3, generator=g))
+    return torch.cat(xs).cuda().contiguous()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    args = ap.parse_args()
+    _capi.load()
+    dev = torch.device("cuda")
+    out = {"device": torch.cuda.get_device_name(0)}
+    for name, G in (("pairwise_64x25", 1), ("pairwise_16x64x25", 16)):
+        x = pocket_cas(G, 64, 100)
+        m = torch.ones(x.shape[:2], dtype=torch.bool, device=dev)
+        pairs, _, _ = geometry.group_pairs(torch.arange(G).repeat_interleave(64))
+        pairs = pairs.to(dev)
+        ours = geometry.superpose(x, x, m, m, pairs)["rmsd"]
+        ref = torch_pairwise(x, m, pairs)
+        out[name] = {"pairs": int(pairs.shape[0]), "max_abs_diff_A": float((ours - ref).abs().max()),
+                     "hip": timed(lambda: geometry.superpose(x, x, m, m, pairs), args.reps),
+                     "torch_svd": timed(lambda: torch_pairwise(x, m, pairs), max(args.reps // 10, 5), graph=False)}
+    B, L, A = 64, 128, 15
+    batch = synth.make_pocket_batch(B, L, 20, seed=7)
+    p2 = batch["pos_heavyatom"].cuda()
+    mask = batch["mask_heavyatom"].cuda()
+    p1 = (p2 + 1.5 * torch.randn(p2.shape, generator=torch.Generator().manual_seed(3)).cuda()).contiguous()
+    ours = geometry.batch_align(p1, p2, mask)[0]
+    ref = torch_batch_align(p1, p2, mask)
+    out["batch_align_64x128x15"] = {"max_abs_diff_A": float((ours - ref).abs().max()),
+                                    "hip": timed(lambda: geometry.batch_align(p1, p2, mask), args.reps),
+                                    "torch_svd": timed(lambda: torch_batch_align(p1, p2, mask), max(args.reps // 10, 5), graph=False)}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
