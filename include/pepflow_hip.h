@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PF_ABI_VERSION 60
+#define PF_ABI_VERSION 61
 #define PF_ATT_VROWS 164             /* rows of a head's transposed value block: 128 channels + 12 points x 3 */
 /* att_vt (f16 mode, ABI 53): a head's transposed values [PF_ATT_VROWS rows][keys] in the FRAGMENT ORDER of the score kernel's second
  * product -- block (tile n, 32-key step) = 512 f16 = the eight operand slots of each of its 64 lanes: row c sits in tile n = c & 7 as
@@ -829,6 +829,37 @@ typedef struct {
     int B, L;
 } pf_binding_site_args;
 int pf_binding_site_fwd(const pf_binding_site_args* a, pf_stream_t stream);
+
+/* ---- TM-score with a fixed residue correspondence (ABI 61) ----------------------------------------------------------------
+ * pf_tm_score_fwd: the TMscore program's search (Zhang & Skolnick, Proteins 2004) over a work list.  Pair p = (i, j) =
+ * pairs[2p], pairs[2p+1] aligns the points n with mx[i,n] & my[j,n], in index order (n_ali of them), and normalises by
+ * Lnorm = sum(my[j]): d0 = max(0.5, 1.24 cbrt(Lnorm - 15) - 1.8), score = sum 1 / (1 + (|R x + t - y| / d0)^2) / Lnorm.
+ * Seeds: contiguous runs of the aligned list of lengths n_ali, n_ali / 2, ... down to min(4, n_ali), every start; each seed is
+ * superposed (proper Kabsch, fp64) and then refined up to 20 times on the points closer than d0_search + 1 (d0_search - 1 after
+ * the seed; d0_search = clamp(d0, 4.5, 8); raised by 0.5 until >= 3 points).  The best-scoring superposition is kept, the first
+ * one in seed / iteration order on equal scores.
+ *   tm[p]          the best score; NaN where n_ali < 3;
+ *   count[p]       n_ali (0 for pair indices outside [0, Bx) x [0, By));  lnorm[p]  Lnorm;
+ *   rot[p] 3x3 row-major, trans[p] 3: the best transform, y ~ rot x + trans, a proper rotation (optional, both or neither;
+ *                  identity / NaN where tm is NaN);
+ *   aligned[p]     rot x[i,n] + trans for ALL n, masked points included ([P,N,3], optional; NaN where tm is NaN).
+ * One lane per (pair, seed), two launches, no host synchronisation.  `work` is caller-owned scratch of
+ * P x pf_tm_score_work_slots(N) x PF_TM_SLOT_BYTES bytes (no initialisation needed).  N > PF_TM_MAX_N -> PF_E_TOOLARGE.  y may alias x.
+ * Results are bit-identical from run to run and do not depend on the order or the company of a pair in the work list. */
+#define PF_TM_MAX_N 512
+#define PF_TM_SLOT_BYTES 112            /* work = P x pf_tm_score_work_slots(N) x PF_TM_SLOT_BYTES bytes */
+typedef struct {
+    const float* x; const float* y;                     /* [Bx,N,3], [By,N,3] */
+    const unsigned char* mx; const unsigned char* my;   /* [Bx,N], [By,N] */
+    const int* pairs;                                   /* [P,2] */
+    float* tm; int* count; int* lnorm;                  /* [P] */
+    float* rot; float* trans;                           /* [P,9], [P,3] optional */
+    float* aligned;                                     /* [P,N,3] optional */
+    void* work;                                         /* scratch, see above */
+    int Bx, By, N, P;
+} pf_tm_score_args;
+int pf_tm_score_fwd(const pf_tm_score_args* a, pf_stream_t stream);
+int pf_tm_score_work_slots(int N);      /* scratch slots per pair (-1 for N outside [1, PF_TM_MAX_N]) */
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,7 @@
 """Superposition on the device: drop-in for `align` / `batch_align` of pepflow/modules/common/geometry.py:18-56 (imported by the
 reference's sampling drivers), Kabsch RMSD and the pairwise RMSD / sequence-identity matrix of a set of samples, on the HIP kernel
-pf_superpose_fwd (one wave per pair of a work list, fp64 sums and 3x3 SVD).
+pf_superpose_fwd (one wave per pair of a work list, fp64 sums and 3x3 SVD); TM-score with a fixed residue correspondence and its
+pairwise matrix on pf_tm_score_fwd (one lane per seed of the TMscore program's search).
 
 Deviation from the reference: `batch_align` selects each sample's masked atoms on their own.  The reference's
 `masked_select(...).reshape(B, -1, 3)` mixes atoms across samples when the per-sample mask counts differ; where the counts are equal
@@ -117,3 +118,72 @@ def pairwise_superpose_rmsd(x, mask, aa=None, groups=None):
         return m.masked_fill(eye, diag)
     rmsd = mirror(out["rmsd"], 0.0)
     return rmsd if aa is None else (rmsd, mirror(out["ident"], 1.0))
+
+
+TM_MAX_N = 512              # PF_TM_MAX_N: the longest point set pf_tm_score_fwd takes
+TM_SLOT_BYTES = 112         # PF_TM_SLOT_BYTES: one scratch slot (the best candidate of 64 seeds)
+
+
+def tm_score(x, y, mx, my, pairs, transform=False, aligned=False):
+    """pf_tm_score_fwd over the work list `pairs` [P,2]: TM-score of x[i] against y[j] with the residue correspondence fixed
+    (the TMscore program's algorithm, Zhang & Skolnick 2004), on the points mx[i] & my[j], normalised by the target's count my[j].
+
+    x [Bx,N,3], y [By,N,3] (y may be x), mx [Bx,N], my [By,N], N <= TM_MAX_N.
+    -> dict of device tensors: tm [P] (NaN where fewer than 3 points are shared), count [P] (shared points; 0 for pair indices out
+    of range), lnorm [P] (the normalising count); rot [P,3,3], trans [P,3] of the best superposition (y ~ rot x + trans, a proper
+    rotation) if `transform`; aligned [P,N,3] (rot x[i] + trans for all N points) if `aligned`."""
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise ValueError(f"x must be [B,N,3], got {tuple(x.shape)}")
+    Bx, N, _ = x.shape
+    By = y.shape[0] if y.dim() == 3 else -1
+    if tuple(y.shape[1:]) != (N, 3) or tuple(mx.shape) != (Bx, N) or tuple(my.shape) != (By, N):
+        raise ValueError(f"shapes do not agree: x {tuple(x.shape)}, y {tuple(y.shape)}, mx {tuple(mx.shape)}, my {tuple(my.shape)}")
+    pairs = torch.as_tensor(pairs)
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"pairs must be [P,2], got {tuple(pairs.shape)}")
+    if N > TM_MAX_N:
+        raise _capi.PepflowHipError(f"tm_score: N = {N} points exceeds the kernel's bound of {TM_MAX_N}")
+    if N == 0 or Bx == 0 or By == 0:
+        raise ValueError("tm_score needs at least one point set of at least one point on each side")
+    dev = x.device
+    keep = [_f32(x, (Bx, N, 3), dev)]
+    keep.append(keep[0] if y is x else _f32(y, (By, N, 3), dev))
+    keep += [_u8(mx, (Bx, N), dev)]
+    keep.append(keep[2] if my is mx else _u8(my, (By, N), dev))
+    pairs = pairs.to(dev, torch.int32).contiguous()
+    P = pairs.shape[0]
+    a = _capi.TmScoreArgs()
+    a.x, a.y, a.mx, a.my = (_capi.dptr(t, t.dtype, nm) for t, nm in zip(keep, ("x", "y", "mx", "my")))
+    a.pairs = _capi.dptr(pairs, torch.int32, "pairs")
+    out = {"tm": torch.empty(P, device=dev), "count": torch.empty(P, dtype=torch.int32, device=dev),
+           "lnorm": torch.empty(P, dtype=torch.int32, device=dev)}
+    if transform:
+        out["rot"], out["trans"] = torch.empty(P, 3, 3, device=dev), torch.empty(P, 3, device=dev)
+    if aligned:
+        out["aligned"] = torch.empty(P, N, 3, device=dev)
+    for k in ("tm", "count", "lnorm", "rot", "trans", "aligned"):
+        if k in out:
+            setattr(a, k, out[k].data_ptr())
+    a.Bx, a.By, a.N, a.P = Bx, By, N, P
+    if P:
+        lib = _capi.load()
+        slots = lib.pf_tm_score_work_slots(N)
+        work = torch.empty(P * slots * TM_SLOT_BYTES, dtype=torch.uint8, device=dev)
+        a.work = work.data_ptr()
+        _capi.check(lib.pf_tm_score_fwd(C.byref(a), _capi.stream_ptr()), "pf_tm_score_fwd")
+    return out
+
+
+def pairwise_tm_score(x, mask, groups=None):
+    """x [B,N,3], mask [B,N] -> tm [B,B]: TM-score of every pair i < j of the same group (all one group when `groups` is None), x[i]
+    onto x[j] normalised by mask[j], mirrored, so the matrix is exactly symmetric with a diagonal of 1; pairs across groups are NaN.
+    Within a group of one complex the masks are equal and the score does not depend on the direction."""
+    B = x.shape[0]
+    dev = x.device
+    pairs, _, _ = group_pairs(torch.zeros(B, dtype=torch.int64) if groups is None else groups)
+    tm = tm_score(x, x, mask, mask, pairs)["tm"]
+    i, j = pairs[:, 0].to(dev, torch.int64), pairs[:, 1].to(dev, torch.int64)
+    m = torch.full((B, B), float("nan"), device=dev)
+    m[i, j] = tm
+    m[j, i] = tm
+    return m.masked_fill(torch.eye(B, dtype=torch.bool, device=dev), 1.0)

@@ -1,17 +1,18 @@
 """Quality metrics of sampled peptides on the device: what the reference's sampling driver reports after `sample()`
 (models_con/inference.py:77-79: CA RMSD, rotation RMSD, amino-acid recovery) and what its evaluation adds (eval/geometry.py:
 CA RMSD after superposition, `get_rmsd` 47-59; binding-site ratio, `get_bind_site` / `get_bind_ratio` 93-110; diversity among the
-samples of one complex), without Biopython / tmtools / mdtraj and without writing PDB files.
+samples of one complex), without Biopython / tmtools / mdtraj and without writing PDB files; TM-score against the native, novelty
+and TM-score diversity (`structure_scores`).
 
-Every per-residue and per-point operation runs in pf_superpose_fwd / pf_binding_site_fwd; the host builds pair lists and masks and
-combines per-sample (or per-pair) outputs."""
+Every per-residue and per-point operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd; the host builds pair
+lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
 import torch
 
 from . import _capi
-from .geometry import group_pairs, superpose
+from .geometry import group_pairs, superpose, tm_score
 
 BIND_CUTOFF = 10.0          # eval/geometry.py:100: receptor residues within 10 A of a peptide CA
 CA_ATOM = 1                 # BBHeavyAtom.CA
@@ -109,3 +110,45 @@ def evaluate_samples(final, batch, groups=None):
             "count": ca["count"], "site_sample": s_site, "site_native": n_site,
             "ca_rmsd_pooled": torch.sqrt(ca_sum / tot), "rot_rmsd_pooled": torch.sqrt(rot_sum / tot), "aar_pooled": same / tot,
             "diversity_rmsd": div_rmsd, "diversity_seq": div_seq, "group_labels": glab.to(dev)}
+
+
+def structure_scores(final, batch, groups=None, novelty_tm=0.5, novelty_ident=0.5):
+    """TM-score of the sampled CAs (`trans`) against the native ones (`trans_1`) over the generated residues, and two combinations
+    of it.  final / batch / groups as in `evaluate_samples` (only final["trans"], ["trans_1"], ["seqs"], ["seqs_1"] and
+    batch["generate_mask"] are read).  The TM-score keeps the residue correspondence fixed (the TMscore program's search, not
+    TM-align's), normalised by the native's generated count (tmtools' tm_norm_chain2).
+
+    -> dict of device tensors:
+      tm           [B] sample onto native (NaN below 3 generated residues);
+      tm_pooled    mean of tm (float64 scalar);
+      novel        [B] bool: tm < novelty_tm and aar < novelty_ident, aar = positional sequence identity to seqs_1 (the fraction of
+                   generated positions with the same residue type; not the reference's difflib ratio);
+      novelty      [G] fraction of novel samples in each group;
+      diversity_tm [G] 1 - mean TM-score over the pairs i < j of the group (sample i onto sample j), NaN for a group of one;
+      group_labels [G].
+    `novel`, `novelty` and `diversity_tm` are this package's definitions, with thresholds of the caller's choosing."""
+    labels = _check_groups(batch["generate_mask"], groups)
+    dev = _device(batch["generate_mask"], final["trans"])
+    final = {k: final[k].to(dev) for k in ("trans", "seqs", "trans_1", "seqs_1")}
+    B = final["seqs"].shape[0]
+    gen = batch["generate_mask"].to(dev).bool()
+    ids = torch.arange(B, dtype=torch.int32)
+    diag = torch.stack([ids, ids], 1)
+
+    tm = tm_score(final["trans"], final["trans_1"], gen, gen, diag)["tm"]
+    aar = superpose(final["trans"], final["trans_1"], gen, gen, diag, aa_x=final["seqs"], aa_y=final["seqs_1"])["ident"]
+    novel = (tm < novelty_tm) & (aar < novelty_ident)
+
+    lab = labels.to(dev)
+    glab, gsam = torch.unique(lab, sorted=True, return_inverse=True)
+    G = glab.numel()
+    nsam = torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gsam, torch.ones(B, dtype=torch.float64, device=dev))
+    novelty = torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gsam, novel.double()) / nsam
+
+    pairs, gidx, _ = group_pairs(labels)
+    gidx = gidx.to(dev)
+    ptm = tm_score(final["trans"], final["trans"], gen, gen, pairs)["tm"]
+    npair = torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, torch.ones_like(gidx, dtype=torch.float64))
+    div_tm = 1.0 - torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, ptm.double()) / npair
+    return {"tm": tm, "tm_pooled": tm.double().mean(), "novel": novel, "novelty": novelty, "diversity_tm": div_tm,
+            "group_labels": glab}

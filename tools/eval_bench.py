@@ -1,18 +1,24 @@
 """Times the evaluation kernels against the same work done with torch ops and torch.linalg.svd on the device.
 
 Cases: the pairwise superposition at 64 samples x 25 CA (2 016 pairs), the same at 16 groups x 64 samples (32 256 pairs), and
-batch_align at B = 64, L = 128, A = 15.  Per case: `call` = device events around REPS back-to-back calls of the Python function
+batch_align at B = 64, L = 128, A = 15.  TM-score (pf_tm_score_fwd): pairwise at 64 samples x 15 and x 25 CA (2 016 pairs each), 16 groups
+x 64 x 25 (32 256 pairs) and 64 sample-vs-native pairs at N = 128, checked against the float64 oracle of tests/tm_oracle.py on the
+CPU (a subset of the pairs; its time per pair is reported).  Per case: `call` = device events around REPS back-to-back calls of the Python function
 (host overhead included), `graph` = the same calls captured once as a graph and replayed (device time per call; HIP only).  Prints one JSON
 line.  Usage: python tools/eval_bench.py [--reps 200]"""
 import argparse
 import json
 import os
 import sys
+import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 from pepflowww_amd import _capi, geometry, synth  # noqa: E402
+import tm_oracle  # noqa: E402
 
 
 def torch_pairwise(x, m, pairs):
@@ -76,15 +82,27 @@ def timed(fn, reps, graph=True):
     return {"call_us": round(call, 2), "graph_us": round(e0.elapsed_time(e1) * 1e3 / reps, 2)}
 
 
-def pocket_cas(n_complex, n_samples, seed):
-    """n_complex x n_samples peptide CA sets of 25 residues (samples of one complex: the native plus 2 A noise)"""
+def pocket_cas(n_complex, n_samples, seed, n=25):
+    """n_complex x n_samples peptide CA sets of n residues (samples of one complex: the native plus 2 A noise)"""
     xs = []
     for c in range(n_complex):
-        batch = synth.make_pocket_batch(1, 60, 25, seed=seed + c)
+        batch = synth.make_pocket_batch(1, max(60, n + 35), n, seed=seed + c)
         ca = batch["pos_heavyatom"][0, batch["generate_mask"][0], 1]
         g = torch.Generator().manual_seed(seed + c)
-        xs.append(ca[None] + 2.0 * torch.randn(n_samples, 25, 3, generator=g))
+        xs.append(ca[None] + 2.0 * torch.randn(n_samples, n, 3, generator=g))
     return torch.cat(xs).cuda().contiguous()
+
+
+def tm_case(x, y, m, pairs, reps, n_check):
+    """pf_tm_score_fwd on the pair list, timed, and checked against the float64 oracle on the first n_check pairs"""
+    ours = geometry.tm_score(x, y, m, m, pairs)["tm"].cpu().double().numpy()
+    xs, ys, ms, pp = x.cpu().numpy(), y.cpu().numpy(), m.cpu().numpy(), pairs.cpu().numpy()
+    t0 = time.perf_counter()
+    ref = np.array([tm_oracle.tm_score(xs[i], ys[j], ms[i], ms[j])["tm"] for i, j in pp[:n_check]])
+    per_pair = (time.perf_counter() - t0) / n_check
+    return {"pairs": int(pairs.shape[0]), "checked": n_check, "max_abs_diff_tm": float(np.abs(ours[:n_check] - ref).max()),
+            "hip": timed(lambda: geometry.tm_score(x, y, m, m, pairs), reps),
+            "oracle_cpu_ms_per_pair": round(per_pair * 1e3, 2)}
 
 
 def main():
@@ -114,6 +132,16 @@ def main():
     out["batch_align_64x128x15"] = {"max_abs_diff_A": float((ours - ref).abs().max()),
                                     "hip": timed(lambda: geometry.batch_align(p1, p2, mask), args.reps),
                                     "torch_svd": timed(lambda: torch_batch_align(p1, p2, mask), max(args.reps // 10, 5), graph=False)}
+    for name, n, G in (("tm_pairwise_64x15", 15, 1), ("tm_pairwise_64x25", 25, 1), ("tm_pairwise_16x64x25", 25, 16)):
+        x = pocket_cas(G, 64, 200, n)
+        m = torch.ones(x.shape[:2], dtype=torch.bool, device=dev)
+        pairs, _, _ = geometry.group_pairs(torch.arange(G).repeat_interleave(64))
+        out[name] = tm_case(x, x, m, pairs.to(dev), args.reps, 64)
+    native = pocket_cas(1, 1, 300, 128).expand(64, 128, 3)
+    sample = (native + 1.5 * torch.randn(native.shape, generator=torch.Generator().manual_seed(5)).cuda()).contiguous()
+    ids = torch.arange(64, dtype=torch.int32, device=dev)
+    out["tm_native_64x128"] = tm_case(sample, native.contiguous(), torch.ones(64, 128, dtype=torch.bool, device=dev),
+                                      torch.stack([ids, ids], 1), args.reps, 8)
     print(json.dumps(out))
 
 
