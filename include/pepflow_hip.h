@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PF_ABI_VERSION 61
+#define PF_ABI_VERSION 62
 #define PF_ATT_VROWS 164             /* rows of a head's transposed value block: 128 channels + 12 points x 3 */
 /* att_vt (f16 mode, ABI 53): a head's transposed values [PF_ATT_VROWS rows][keys] in the FRAGMENT ORDER of the score kernel's second
  * product -- block (tile n, 32-key step) = 512 f16 = the eight operand slots of each of its 64 lanes: row c sits in tile n = c & 7 as
@@ -860,6 +860,32 @@ typedef struct {
 } pf_tm_score_args;
 int pf_tm_score_fwd(const pf_tm_score_args* a, pf_stream_t stream);
 int pf_tm_score_work_slots(int N);      /* scratch slots per pair (-1 for N outside [1, PF_TM_MAX_N]) */
+
+/* ---- DSSP secondary structure (ABI 62) ------------------------------------------------------------------------------------
+ * pf_dssp_fwd: DSSP (Kabsch & Sander, Biopolymers 1983) of B chain slots of N residues, DSSP 2.x conventions (csrc/dssp.hip
+ * lists them), geometry in fp64 from the fp32 inputs.  pos [B,N,n_atoms,3] with atoms 0..3 = N, CA, C, O (BBHeavyAtom order, so
+ * pos_heavyatom is read as it is; n_atoms >= 4); mask [B,N] the residues taken part; chain [B,N] optional (a change of id breaks
+ * the chain); aa [B,N] optional, only to find prolines (aa == pro: not an H-bond donor).
+ *   ss [B,N]            8-state codes H 0, B 1, E 2, G 3, I 4, T 5, S 6, '-' 7 (SSTRUCT_SYMB_TO_INDEX of the reference's
+ *                       pepflow/modules/protein/dssp.py); 255 where mask is false;
+ *   hb_acc [B,N,2]      each donor's two lowest-energy acceptors below 0 kcal/mol (-1: none) and hb_energy [B,N,2] their
+ *                       energies (0 with -1); a bond where E < -0.5 (optional, both or neither).
+ * One workgroup per slot, one launch, no host synchronisation.  Results do not depend on the other rows and are bit-identical
+ * from run to run.  N > PF_DSSP_MAX_N -> PF_E_TOOLARGE.
+ * PF_DSSP_PI_PRECEDENCE 1: a pi-helix may overwrite H (DSSP >= 2.1); the older rule leaves H in place. */
+#define PF_DSSP_MAX_N 512
+#define PF_DSSP_PI_PRECEDENCE 1
+typedef struct {
+    const float* pos;                   /* [B,N,n_atoms,3] */
+    const unsigned char* mask;          /* [B,N] */
+    const int64_t* chain;               /* [B,N] optional */
+    const int64_t* aa;                  /* [B,N] optional */
+    unsigned char* ss;                  /* [B,N] */
+    int* hb_acc;                        /* [B,N,2] optional */
+    float* hb_energy;                   /* [B,N,2] optional */
+    int B, N, n_atoms, pro;             /* pro: the residue index of proline */
+} pf_dssp_args;
+int pf_dssp_fwd(const pf_dssp_args* a, pf_stream_t stream);
 
 #ifdef __cplusplus
 }

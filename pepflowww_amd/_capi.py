@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (PF_LIB_PATH: another build of the same library -- same-box A/B runs of kernel variants, tools/dev)
 LIB_PATH = os.environ.get("PF_LIB_PATH") or os.path.join(_HERE, "lib", "libpepflow_hip.so")
-ABI_VERSION = 61
+ABI_VERSION = 62
 
 _fp = C.c_void_p
 _i = C.c_int
@@ -184,6 +184,11 @@ class TmScoreArgs(C.Structure):
                 ("rot", _fp), ("trans", _fp), ("aligned", _fp), ("work", _fp), ("Bx", _i), ("By", _i), ("N", _i), ("P", _i)]
 
 
+class DsspArgs(C.Structure):
+    _fields_ = [("pos", _fp), ("mask", _fp), ("chain", _fp), ("aa", _fp), ("ss", _fp), ("hb_acc", _fp), ("hb_energy", _fp),
+                ("B", _i), ("N", _i), ("n_atoms", _i), ("pro", _i)]
+
+
 class EtBwdArgs(C.Structure):
     _fields_ = [("g_y", _fp), ("h1", _fp), ("h2", _fp), ("wfT_f16", _fp), ("w2T_f16", _fp), ("w1T_f16", _fp),
                 ("g_h2", _fp), ("g_h1", _fp), ("g_x", _fp), ("npairs", C.c_longlong), ("m1", _fp), ("m2", _fp)]
@@ -261,6 +266,7 @@ _SIGNATURES = {
     "pf_binding_site_fwd": ([C.POINTER(BindingSiteArgs), _fp], _i),
     "pf_tm_score_fwd": ([C.POINTER(TmScoreArgs), _fp], _i),
     "pf_tm_score_work_slots": ([_i], _i),
+    "pf_dssp_fwd": ([C.POINTER(DsspArgs), _fp], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

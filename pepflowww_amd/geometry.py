@@ -1,7 +1,8 @@
 """Superposition on the device: drop-in for `align` / `batch_align` of pepflow/modules/common/geometry.py:18-56 (imported by the
 reference's sampling drivers), Kabsch RMSD and the pairwise RMSD / sequence-identity matrix of a set of samples, on the HIP kernel
 pf_superpose_fwd (one wave per pair of a work list, fp64 sums and 3x3 SVD); TM-score with a fixed residue correspondence and its
-pairwise matrix on pf_tm_score_fwd (one lane per seed of the TMscore program's search).
+pairwise matrix on pf_tm_score_fwd (one lane per seed of the TMscore program's search); DSSP secondary structure on pf_dssp_fwd
+(one workgroup per chain slot).
 
 Deviation from the reference: `batch_align` selects each sample's masked atoms on their own.  The reference's
 `masked_select(...).reshape(B, -1, 3)` mixes atoms across samples when the per-sample mask counts differ; where the counts are equal
@@ -187,3 +188,77 @@ def pairwise_tm_score(x, mask, groups=None):
     m[i, j] = tm
     m[j, i] = tm
     return m.masked_fill(torch.eye(B, dtype=torch.bool, device=dev), 1.0)
+
+
+DSSP_MAX_N = 512            # PF_DSSP_MAX_N: the longest chain slot pf_dssp_fwd takes
+SS_SYMBOLS = "HBEGITS-"     # 8-state codes 0..7: SSTRUCT_SYMB_TO_INDEX of pepflow/modules/protein/dssp.py
+SS_SIMPLE = "HEC"           # simplified codes 0..2 (mdtraj's compute_dssp(simplified=True))
+SS_MASKED = 255
+# 8-state -> simplified: H, G, I -> 0 'H'; E, B -> 1 'E'; T, S, '-' -> 2 'C'; anything else (255 masked) -> 255
+_SIMPLIFY = {}
+
+
+def dssp(pos, mask, chain=None, aa=None, hbonds=False):
+    """pf_dssp_fwd: DSSP 8-state secondary structure of each row (DSSP 2.x conventions, listed in csrc/dssp.hip).
+
+    pos [B,N,A,3] with atoms 0..3 = N, CA, C, O (pos_heavyatom is read as it is), A >= 4; mask [B,N] the residues taken part;
+    chain [B,N] (optional: a change of id breaks the chain); aa [B,N] (optional, only to find prolines, which are no H-bond donors).
+    N <= DSSP_MAX_N.
+    -> ss [B,N] uint8 device tensor (codes of SS_SYMBOLS, 255 where mask is false); with `hbonds` also hb_acc [B,N,2] int32 (each
+    donor's two lowest-energy acceptors below 0 kcal/mol, -1: none) and hb_energy [B,N,2] float32 (0 with -1): (ss, hb_acc,
+    hb_energy).  A bond is an entry with energy < -0.5."""
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 4 or pos.shape[3] != 3 or pos.shape[2] < 4:
+        raise ValueError(f"pos must be [B,N,A,3] with A >= 4 (N, CA, C, O first), got {tuple(getattr(pos, 'shape', ()))}")
+    B, N, A, _ = pos.shape
+    if tuple(mask.shape) != (B, N):
+        raise ValueError(f"mask must be [B,N] = {(B, N)}, got {tuple(mask.shape)}")
+    for nm, t in (("chain", chain), ("aa", aa)):
+        if t is not None and tuple(t.shape) != (B, N):
+            raise ValueError(f"{nm} must be [B,N] = {(B, N)}, got {tuple(t.shape)}")
+    if N > DSSP_MAX_N:
+        raise ValueError(f"dssp: N = {N} residues exceeds the kernel's bound of {DSSP_MAX_N}")
+    dev = pos.device
+    keep = [pos.to(dev, torch.float32).contiguous(), _u8(mask, (B, N), dev)]
+    a = _capi.DsspArgs()
+    a.pos, a.mask = _capi.dptr(keep[0], torch.float32, "pos"), _capi.dptr(keep[1], torch.uint8, "mask")
+    if chain is not None:
+        keep.append(chain.to(dev, torch.int64).contiguous())
+        a.chain = keep[-1].data_ptr()
+    if aa is not None:
+        keep.append(aa.to(dev, torch.int64).contiguous())
+        a.aa = keep[-1].data_ptr()
+    ss = torch.empty(B, N, dtype=torch.uint8, device=dev)
+    a.ss = ss.data_ptr()
+    if hbonds:
+        acc, en = torch.empty(B, N, 2, dtype=torch.int32, device=dev), torch.empty(B, N, 2, device=dev)
+        a.hb_acc, a.hb_energy = acc.data_ptr(), en.data_ptr()
+    a.B, a.N, a.n_atoms, a.pro = B, N, A, _proline()
+    if B and N:
+        _capi.check(_capi.load().pf_dssp_fwd(C.byref(a), _capi.stream_ptr()), "pf_dssp_fwd")
+    return (ss, acc, en) if hbonds else ss
+
+
+def _proline():
+    from .preprocess import residue_type
+    return residue_type("PRO")
+
+
+def ss_simplify(ss):
+    """8-state codes -> mdtraj's simplified ones: 0 'H' (H, G, I), 1 'E' (E, B), 2 'C' (T, S, '-'); 255 stays 255"""
+    key = str(ss.device)
+    if key not in _SIMPLIFY:
+        t = torch.full((256,), SS_MASKED, dtype=torch.uint8)
+        t[:8] = torch.tensor([0, 1, 1, 0, 0, 2, 2, 2], dtype=torch.uint8)
+        _SIMPLIFY[key] = t.to(ss.device)
+    return _SIMPLIFY[key][ss.long()]
+
+
+def ss_strings(ss, simplified=False):
+    """ss [B,N] 8-state codes -> one string per row, a character per unmasked residue ("HBEGITS-", or "HEC" with `simplified`),
+    masked residues left out: what joining mdtraj's per-residue codes of the sliced chain gives (with '-' for its ' ')."""
+    if simplified:
+        ss, sym = ss_simplify(ss), SS_SIMPLE
+    else:
+        sym = SS_SYMBOLS
+    rows = ss.reshape(-1, ss.shape[-1]).cpu().tolist()
+    return ["".join(sym[c] for c in row if c < len(sym)) for row in rows]

@@ -2,17 +2,18 @@
 (models_con/inference.py:77-79: CA RMSD, rotation RMSD, amino-acid recovery) and what its evaluation adds (eval/geometry.py:
 CA RMSD after superposition, `get_rmsd` 47-59; binding-site ratio, `get_bind_site` / `get_bind_ratio` 93-110; diversity among the
 samples of one complex), without Biopython / tmtools / mdtraj and without writing PDB files; TM-score against the native, novelty
-and TM-score diversity (`structure_scores`).
+and TM-score diversity (`structure_scores`); DSSP secondary structure and the secondary-structure ratio, `get_second_stru` / `get_ss`
+79-91 (`secondary_structure`).
 
-Every per-residue and per-point operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd; the host builds pair
-lists and masks and combines per-sample (or per-pair) outputs."""
+Every per-residue and per-point operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd (and the
+backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
 import torch
 
-from . import _capi
-from .geometry import group_pairs, superpose, tm_score
+from . import _capi, full_atom
+from .geometry import dssp, group_pairs, ss_simplify, superpose, tm_score
 
 BIND_CUTOFF = 10.0          # eval/geometry.py:100: receptor residues within 10 A of a peptide CA
 CA_ATOM = 1                 # BBHeavyAtom.CA
@@ -152,3 +153,41 @@ def structure_scores(final, batch, groups=None, novelty_tm=0.5, novelty_ident=0.
     div_tm = 1.0 - torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, ptm.double()) / npair
     return {"tm": tm, "tm_pooled": tm.double().mean(), "novel": novel, "novelty": novelty, "diversity_tm": div_tm,
             "group_labels": glab}
+
+
+def secondary_structure(final, batch, backbone="full_atom"):
+    """DSSP of the peptide chain of each sample and of its native, and the secondary-structure ratio of eval/geometry.py:79-91
+    (`get_second_stru` / `get_ss`: mdtraj's simplified codes, the fraction of peptide residues that agree).  final / batch as in
+    `evaluate_samples`; the peptide chain is generate_mask & res_mask.
+
+    backbone: "full_atom" -- the sample's N, CA, C, O from full_atom_reconstruction(rotmats, trans, angles, seqs), as save_samples_sc
+    writes them; "frames" -- from reconstruct_backbone(rotmats, trans, seqs, chain_nb, res_nb, res_mask), as save_samples_bb does.
+    Prolines come from seqs for the sample and from seqs_1 for the native, whose backbone is pos_heavyatom[..., :4, :]; a native
+    residue missing one of those four atoms in mask_heavyatom counts as masked (and never agrees).
+
+    -> dict of device tensors: ss_sample, ss_native [B,L] uint8 8-state codes (255 off the peptide); ssr [B] the fraction of
+    generated residues whose simplified codes agree (NaN for a sample without any); ssr_pooled the mean of ssr over the samples
+    that have generated residues (float64 scalar); helix, strand, coil [B] the fractions of the sample's generated residues with
+    simplified code H, E, C."""
+    if backbone not in ("full_atom", "frames"):
+        raise ValueError(f"backbone must be 'full_atom' or 'frames', got {backbone!r}")
+    dev = _device(batch["generate_mask"], final["trans"], batch["pos_heavyatom"])
+    gen = batch["generate_mask"].to(dev).bool() & batch["res_mask"].to(dev).bool()
+    chain = batch["chain_nb"].to(dev) if "chain_nb" in batch else None
+    rotmats, trans, seqs = (final[k].to(dev) for k in ("rotmats", "trans", "seqs"))
+    if backbone == "full_atom":
+        bb = full_atom.full_atom_reconstruction(rotmats, trans, final["angles"].to(dev), seqs)[0]
+    else:
+        bb = full_atom.reconstruct_backbone(rotmats, trans, seqs, batch["chain_nb"].to(dev), batch["res_nb"].to(dev),
+                                            batch["res_mask"].to(dev))
+    pos = batch["pos_heavyatom"].to(dev)
+    native_ok = gen & batch["mask_heavyatom"].to(dev)[:, :, :4].bool().all(-1)
+    ss_s = dssp(bb, gen, chain, seqs)
+    ss_n = dssp(pos, native_ok, chain, final["seqs_1"].to(dev))
+    s_s, s_n = ss_simplify(ss_s), ss_simplify(ss_n)
+    n = gen.sum(1).double()
+    ssr = ((s_s == s_n) & native_ok).sum(1).double() / n
+    frac = [((s_s == c) & gen).sum(1).double() / n for c in range(3)]
+    pooled = torch.nan_to_num(ssr).sum() / (n > 0).sum()
+    return {"ss_sample": ss_s, "ss_native": ss_n, "ssr": ssr, "ssr_pooled": pooled,
+            "helix": frac[0], "strand": frac[1], "coil": frac[2]}

@@ -3,7 +3,9 @@
 Cases: the pairwise superposition at 64 samples x 25 CA (2 016 pairs), the same at 16 groups x 64 samples (32 256 pairs), and
 batch_align at B = 64, L = 128, A = 15.  TM-score (pf_tm_score_fwd): pairwise at 64 samples x 15 and x 25 CA (2 016 pairs each), 16 groups
 x 64 x 25 (32 256 pairs) and 64 sample-vs-native pairs at N = 128, checked against the float64 oracle of tests/tm_oracle.py on the
-CPU (a subset of the pairs; its time per pair is reported).  Per case: `call` = device events around REPS back-to-back calls of the Python function
+CPU (a subset of the pairs; its time per pair is reported).  DSSP (pf_dssp_fwd): 4 096 chains x 25 residues (64 complexes x 64
+samples), 64 x 128 and 8 x 512 NeRF chains, checked against the float64 oracle of tests/dssp_oracle.py on a subset of the chains (its
+CPU time per chain is reported), and metrics.secondary_structure at 64 samples x 25 generated residues.  Per case: `call` = device events around REPS back-to-back calls of the Python function
 (host overhead included), `graph` = the same calls captured once as a graph and replayed (device time per call; HIP only).  Prints one JSON
 line.  Usage: python tools/eval_bench.py [--reps 200]"""
 import argparse
@@ -17,7 +19,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-from pepflowww_amd import _capi, geometry, synth  # noqa: E402
+from pepflowww_amd import _capi, geometry, metrics, synth  # noqa: E402
+import dssp_build  # noqa: E402
+import dssp_oracle  # noqa: E402
 import tm_oracle  # noqa: E402
 
 
@@ -105,6 +109,28 @@ def tm_case(x, y, m, pairs, reps, n_check):
             "oracle_cpu_ms_per_pair": round(per_pair * 1e3, 2)}
 
 
+def dssp_chains(n_native, n_samples, n, seed):
+    """n_native NeRF chains of n residues (phi / psi per segment from the helix, strand and coil basins), each repeated n_samples
+    times with 0.3 A of noise -> pos [n_native * n_samples, n, 4, 3] on the device"""
+    rng = np.random.default_rng(seed)
+    nat = np.stack([dssp_build.random_chain(rng, n) for _ in range(n_native)])
+    pos = nat[:, None] + 0.3 * rng.standard_normal((n_native, n_samples, n, 4, 3))
+    return torch.from_numpy(pos.reshape(-1, n, 4, 3).astype(np.float32)).cuda()
+
+
+def dssp_case(pos, reps, n_check):
+    """pf_dssp_fwd on all chains, timed, and checked against the float64 oracle on the first n_check chains"""
+    mask = torch.ones(pos.shape[:2], dtype=torch.bool, device=pos.device)
+    ss = geometry.dssp(pos, mask).cpu().numpy()
+    host = pos.cpu().double().numpy()
+    t0 = time.perf_counter()
+    ref = [dssp_oracle.dssp(host[b], np.ones(pos.shape[1], bool)) for b in range(n_check)]
+    per_chain = (time.perf_counter() - t0) / n_check
+    return {"chains": int(pos.shape[0]), "residues": int(pos.shape[1]), "checked": n_check,
+            "mismatched": int(sum(not np.array_equal(ss[b], r["ss"]) for b, r in enumerate(ref))),
+            "hip": timed(lambda: geometry.dssp(pos, mask), reps), "oracle_cpu_ms_per_chain": round(per_chain * 1e3, 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
@@ -142,6 +168,16 @@ def main():
     ids = torch.arange(64, dtype=torch.int32, device=dev)
     out["tm_native_64x128"] = tm_case(sample, native.contiguous(), torch.ones(64, 128, dtype=torch.bool, device=dev),
                                       torch.stack([ids, ids], 1), args.reps, 8)
+    out["dssp_4096x25"] = dssp_case(dssp_chains(64, 64, 25, 400), args.reps, 64)
+    out["dssp_64x128"] = dssp_case(dssp_chains(64, 1, 128, 401), args.reps, 16)
+    out["dssp_8x512"] = dssp_case(dssp_chains(8, 1, 512, 402), args.reps, 4)
+    batch = {k: v.cuda() for k, v in synth.make_pocket_batch(64, 60, 25, seed=403).items()}
+    rot = torch.linalg.qr(torch.randn(64, 60, 3, 3, generator=torch.Generator().manual_seed(404)))[0].cuda()
+    final = {"rotmats": rot, "trans": batch["pos_heavyatom"][:, :, 1].contiguous(), "angles": batch["torsion_angle"],
+             "seqs": batch["aa"], "seqs_1": batch["aa"]}
+    for bb in ("full_atom", "frames"):
+        out[f"secondary_structure_64x25_{bb}"] = {"hip": timed(lambda: metrics.secondary_structure(final, batch, backbone=bb),
+                                                               args.reps, graph=False)}
     print(json.dumps(out))
 
 
