@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PF_ABI_VERSION 62
+#define PF_ABI_VERSION 63
 #define PF_ATT_VROWS 164             /* rows of a head's transposed value block: 128 channels + 12 points x 3 */
 /* att_vt (f16 mode, ABI 53): a head's transposed values [PF_ATT_VROWS rows][keys] in the FRAGMENT ORDER of the score kernel's second
  * product -- block (tile n, 32-key step) = 512 f16 = the eight operand slots of each of its 64 lanes: row c sits in tile n = c & 7 as
@@ -886,6 +886,41 @@ typedef struct {
     int B, N, n_atoms, pro;             /* pro: the residue index of proline */
 } pf_dssp_args;
 int pf_dssp_fwd(const pf_dssp_args* a, pf_stream_t stream);
+
+/* ---- TM-align structural alignment (ABI 63) -------------------------------------------------------------------------------
+ * pf_tm_align_fwd: TM-align (Zhang & Skolnick, Nucleic Acids Res. 2005) over a work list: a sequence-independent alignment of
+ * the CA traces, fp64 from the fp32 inputs.  Pair p = (i, j) = pairs[2p], pairs[2p+1] aligns chain 1 = x[i] on mx[i] (the model,
+ * Lx residues in index order) to chain 2 = y[j] on my[j] (the target, Ly residues).  The conventions (search parameters, DP, TM
+ * searches, the five initial alignments, the degenerate-fit rule) are listed in csrc/tm_align.hip.
+ *   tm[p]          TM-score of the final alignment normalised by Ly (tmtools' tm_norm_chain2); NaN where Lx < 3 or Ly < 3;
+ *   tm_x[p]        the same normalised by Lx (tm_norm_chain1);
+ *   rmsd[p]        Kabsch RMSD of the n_aligned pairs (NaN when there are none);
+ *   n_aligned[p]   aligned pairs within score_d8 under the final superposition (TM-align's n_ali8); 0 for pair indices
+ *                  outside [0, Bx) x [0, By); -1 when Lx or Ly exceeds max_len (then every score is NaN);
+ *   len_x[p], len_y[p]  Lx, Ly;
+ *   rot[p] 3x3 row-major, trans[p] 3: the transform of the search behind tm, y ~ rot x + trans (optional, both or neither;
+ *                  identity / NaN where tm is NaN);
+ *   y2x[p,n]       for each of y's N positions the aligned position of x (an index into N), -1 unaligned or masked, and kept[p,n]
+ *                  1 at the y positions of the n_aligned pairs (optional, both or neither);
+ *   aligned[p]     rot x[i,n] + trans for ALL n ([P,N,3], optional).
+ * One wave per pair, one launch, no host synchronisation, no scratch.  LDS is sized by max_len, an upper bound on Lx and Ly that
+ * the caller may give (0: N); pf_tm_align_lds_bytes(max_len) gives the size (117 KiB at 512).  N > PF_TM_ALIGN_MAX_N ->
+ * PF_E_TOOLARGE.  y may alias x.  Results are bit-identical from run to run and do not depend on the rest of the work list. */
+#define PF_TM_ALIGN_MAX_N 512
+typedef struct {
+    const float* x; const float* y;                     /* [Bx,N,3], [By,N,3] */
+    const unsigned char* mx; const unsigned char* my;   /* [Bx,N], [By,N] */
+    const int* pairs;                                   /* [P,2] */
+    float* tm; float* tm_x; float* rmsd;                /* [P] */
+    int* n_aligned; int* len_x; int* len_y;             /* [P] */
+    float* rot; float* trans;                           /* [P,9], [P,3] optional */
+    int* y2x; unsigned char* kept;                      /* [P,N] optional */
+    float* aligned;                                     /* [P,N,3] optional */
+    int Bx, By, N, P;
+    int max_len;                                        /* bound on the compacted lengths, 0: N */
+} pf_tm_align_args;
+int pf_tm_align_fwd(const pf_tm_align_args* a, pf_stream_t stream);
+int pf_tm_align_lds_bytes(int max_len);        /* dynamic LDS of one pair's workgroup (0 for max_len outside [1, PF_TM_ALIGN_MAX_N]) */
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (PF_LIB_PATH: another build of the same library -- same-box A/B runs of kernel variants, tools/dev)
 LIB_PATH = os.environ.get("PF_LIB_PATH") or os.path.join(_HERE, "lib", "libpepflow_hip.so")
-ABI_VERSION = 62
+ABI_VERSION = 63
 
 _fp = C.c_void_p
 _i = C.c_int
@@ -189,6 +189,12 @@ class DsspArgs(C.Structure):
                 ("B", _i), ("N", _i), ("n_atoms", _i), ("pro", _i)]
 
 
+class TmAlignArgs(C.Structure):
+    _fields_ = [("x", _fp), ("y", _fp), ("mx", _fp), ("my", _fp), ("pairs", _fp), ("tm", _fp), ("tm_x", _fp), ("rmsd", _fp),
+                ("n_aligned", _fp), ("len_x", _fp), ("len_y", _fp), ("rot", _fp), ("trans", _fp), ("y2x", _fp), ("kept", _fp),
+                ("aligned", _fp), ("Bx", _i), ("By", _i), ("N", _i), ("P", _i), ("max_len", _i)]
+
+
 class EtBwdArgs(C.Structure):
     _fields_ = [("g_y", _fp), ("h1", _fp), ("h2", _fp), ("wfT_f16", _fp), ("w2T_f16", _fp), ("w1T_f16", _fp),
                 ("g_h2", _fp), ("g_h1", _fp), ("g_x", _fp), ("npairs", C.c_longlong), ("m1", _fp), ("m2", _fp)]
@@ -267,6 +273,8 @@ _SIGNATURES = {
     "pf_tm_score_fwd": ([C.POINTER(TmScoreArgs), _fp], _i),
     "pf_tm_score_work_slots": ([_i], _i),
     "pf_dssp_fwd": ([C.POINTER(DsspArgs), _fp], _i),
+    "pf_tm_align_fwd": ([C.POINTER(TmAlignArgs), _fp], _i),
+    "pf_tm_align_lds_bytes": ([_i], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -190,6 +190,91 @@ def pairwise_tm_score(x, mask, groups=None):
     return m.masked_fill(torch.eye(B, dtype=torch.bool, device=dev), 1.0)
 
 
+TM_ALIGN_MAX_N = 512        # PF_TM_ALIGN_MAX_N: the most slots pf_tm_align_fwd takes
+
+
+def tm_align(x, y, mx, my, pairs, transform=False, alignment=False, aligned=False, max_len=None):
+    """pf_tm_align_fwd: TM-align (Zhang & Skolnick 2005) of chain 1 = x[i] on mx[i] (the model) onto chain 2 = y[j] on my[j] (the
+    target) for every pair (i, j) of `pairs` [P,2]: a sequence-independent alignment of the CA traces, in fp64 on the device.  The
+    conventions are listed in csrc/tm_align.hip.
+
+    x [Bx,N,3], y [By,N,3] (y may be x), mx [Bx,N], my [By,N], N <= TM_ALIGN_MAX_N.  max_len: an optional upper bound on the
+    unmasked counts, which sizes the kernel's LDS (a 25-residue peptide in 256 slots needs only 25); a pair above it returns NaN and
+    n_aligned -1.
+    -> dict of device tensors, with tmtools' TMResult names alongside:
+      tm [P]          normalised by chain 2's length Ly: tmtools' tm_norm_chain2 (what eval/geometry.py's get_tm returns);
+      tm_x [P]        normalised by Lx: tm_norm_chain1;
+      rmsd [P]        Kabsch RMSD of the n_aligned pairs: rmsd;
+      n_aligned [P]   pairs within score_d8 after the final superposition (TM-align's n_ali8; -1 above max_len);
+      len_x, len_y [P];
+      rot [P,3,3], trans [P,3] (`transform`): the superposition of the search behind tm, y ~ rot x + trans -- tmtools' u, t
+                      correspond to it, but which of the program's final searches tmtools copies out cannot be checked here;
+      y2x [P,N] int32, kept [P,N] bool (`alignment`): for each y position the aligned x position (an index into N, -1 none) and
+                      whether the pair counts in n_aligned; seqxA / seqyA follow from y2x;
+      aligned [P,N,3] (`aligned`): rot x + trans for all N points.
+    NaN scores where a chain has fewer than 3 residues or the pair indices are out of range (n_aligned 0)."""
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise ValueError(f"x must be [B,N,3], got {tuple(x.shape)}")
+    Bx, N, _ = x.shape
+    By = y.shape[0] if y.dim() == 3 else -1
+    if tuple(y.shape[1:]) != (N, 3) or tuple(mx.shape) != (Bx, N) or tuple(my.shape) != (By, N):
+        raise ValueError(f"shapes do not agree: x {tuple(x.shape)}, y {tuple(y.shape)}, mx {tuple(mx.shape)}, my {tuple(my.shape)}")
+    pairs = torch.as_tensor(pairs)
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"pairs must be [P,2], got {tuple(pairs.shape)}")
+    if N > TM_ALIGN_MAX_N:
+        raise _capi.PepflowHipError(f"tm_align: N = {N} points exceeds the kernel's bound of {TM_ALIGN_MAX_N}")
+    if N == 0 or Bx == 0 or By == 0:
+        raise ValueError("tm_align needs at least one chain of at least one point on each side")
+    if max_len is not None and not (0 <= int(max_len)):
+        raise ValueError(f"max_len must be >= 0, got {max_len}")
+    dev = x.device
+    keep = [_f32(x, (Bx, N, 3), dev)]
+    keep.append(keep[0] if y is x else _f32(y, (By, N, 3), dev))
+    keep += [_u8(mx, (Bx, N), dev)]
+    keep.append(keep[2] if my is mx else _u8(my, (By, N), dev))
+    pairs = pairs.to(dev, torch.int32).contiguous()
+    P = pairs.shape[0]
+    a = _capi.TmAlignArgs()
+    a.x, a.y, a.mx, a.my = (_capi.dptr(t, t.dtype, nm) for t, nm in zip(keep, ("x", "y", "mx", "my")))
+    a.pairs = _capi.dptr(pairs, torch.int32, "pairs")
+    out = {"tm": torch.empty(P, device=dev), "tm_x": torch.empty(P, device=dev), "rmsd": torch.empty(P, device=dev)}
+    for k in ("n_aligned", "len_x", "len_y"):
+        out[k] = torch.empty(P, dtype=torch.int32, device=dev)
+    if transform:
+        out["rot"], out["trans"] = torch.empty(P, 3, 3, device=dev), torch.empty(P, 3, device=dev)
+    if alignment:
+        out["y2x"], out["kept"] = torch.empty(P, N, dtype=torch.int32, device=dev), torch.empty(P, N, dtype=torch.uint8, device=dev)
+    if aligned:
+        out["aligned"] = torch.empty(P, N, 3, device=dev)
+    for k in ("tm", "tm_x", "rmsd", "n_aligned", "len_x", "len_y", "rot", "trans", "y2x", "kept", "aligned"):
+        if k in out:
+            setattr(a, k, out[k].data_ptr())
+    a.Bx, a.By, a.N, a.P = Bx, By, N, P
+    a.max_len = 0 if max_len is None else min(int(max_len), N)
+    if P:
+        _capi.check(_capi.load().pf_tm_align_fwd(C.byref(a), _capi.stream_ptr()), "pf_tm_align_fwd")
+    if alignment:
+        out["kept"] = out["kept"].bool()
+    return out
+
+
+def pairwise_tm_align(x, mask, groups=None):
+    """x [B,N,3], mask [B,N] -> tm [B,B]: TM-align of every pair i < j of the same group (all one group when `groups` is None), x[i]
+    onto x[j], normalised by chain j's length, mirrored as pairwise_tm_score is, with a diagonal of 1; pairs across groups are NaN.
+    Unlike the fixed-correspondence TM-score, TM-align's score may depend on the direction; the i-onto-j one is kept."""
+    B = x.shape[0]
+    dev = x.device
+    pairs, _, _ = group_pairs(torch.zeros(B, dtype=torch.int64) if groups is None else groups)
+    max_len = int(torch.as_tensor(mask).bool().sum(1).max()) if B else 0
+    tm = tm_align(x, x, mask, mask, pairs, max_len=max_len)["tm"]
+    i, j = pairs[:, 0].to(dev, torch.int64), pairs[:, 1].to(dev, torch.int64)
+    m = torch.full((B, B), float("nan"), device=dev)
+    m[i, j] = tm
+    m[j, i] = tm
+    return m.masked_fill(torch.eye(B, dtype=torch.bool, device=dev), 1.0)
+
+
 DSSP_MAX_N = 512            # PF_DSSP_MAX_N: the longest chain slot pf_dssp_fwd takes
 SS_SYMBOLS = "HBEGITS-"     # 8-state codes 0..7: SSTRUCT_SYMB_TO_INDEX of pepflow/modules/protein/dssp.py
 SS_SIMPLE = "HEC"           # simplified codes 0..2 (mdtraj's compute_dssp(simplified=True))

@@ -13,7 +13,7 @@ import math
 import torch
 
 from . import _capi, full_atom
-from .geometry import dssp, group_pairs, ss_simplify, superpose, tm_score
+from .geometry import dssp, group_pairs, ss_simplify, superpose, tm_align, tm_score
 
 BIND_CUTOFF = 10.0          # eval/geometry.py:100: receptor residues within 10 A of a peptide CA
 CA_ATOM = 1                 # BBHeavyAtom.CA
@@ -113,7 +113,7 @@ def evaluate_samples(final, batch, groups=None):
             "diversity_rmsd": div_rmsd, "diversity_seq": div_seq, "group_labels": glab.to(dev)}
 
 
-def structure_scores(final, batch, groups=None, novelty_tm=0.5, novelty_ident=0.5):
+def structure_scores(final, batch, groups=None, novelty_tm=0.5, novelty_ident=0.5, tm_mode="fixed"):
     """TM-score of the sampled CAs (`trans`) against the native ones (`trans_1`) over the generated residues, and two combinations
     of it.  final / batch / groups as in `evaluate_samples` (only final["trans"], ["trans_1"], ["seqs"], ["seqs_1"] and
     batch["generate_mask"] are read).  The TM-score keeps the residue correspondence fixed (the TMscore program's search, not
@@ -127,7 +127,13 @@ def structure_scores(final, batch, groups=None, novelty_tm=0.5, novelty_ident=0.
       novelty      [G] fraction of novel samples in each group;
       diversity_tm [G] 1 - mean TM-score over the pairs i < j of the group (sample i onto sample j), NaN for a group of one;
       group_labels [G].
-    `novel`, `novelty` and `diversity_tm` are this package's definitions, with thresholds of the caller's choosing."""
+    `novel`, `novelty` and `diversity_tm` are this package's definitions, with thresholds of the caller's choosing.
+
+    tm_mode: "fixed" (the default) -- the fixed-correspondence TM-score above; "tmalign" -- TM-align (geometry.tm_align): tm is the
+    sample aligned onto the native normalised by the native's length (tmtools' tm_norm_chain2, what eval/geometry.py's get_tm
+    returns), and novel, novelty and diversity_tm (sample i aligned onto sample j) use it.  The keys are the same in both modes."""
+    if tm_mode not in ("fixed", "tmalign"):
+        raise ValueError(f"tm_mode must be 'fixed' or 'tmalign', got {tm_mode!r}")
     labels = _check_groups(batch["generate_mask"], groups)
     dev = _device(batch["generate_mask"], final["trans"])
     final = {k: final[k].to(dev) for k in ("trans", "seqs", "trans_1", "seqs_1")}
@@ -136,7 +142,12 @@ def structure_scores(final, batch, groups=None, novelty_tm=0.5, novelty_ident=0.
     ids = torch.arange(B, dtype=torch.int32)
     diag = torch.stack([ids, ids], 1)
 
-    tm = tm_score(final["trans"], final["trans_1"], gen, gen, diag)["tm"]
+    if tm_mode == "tmalign":
+        max_len = int(gen.sum(1).max()) if B else 0
+        score = lambda x, y, pp: tm_align(x, y, gen, gen, pp, max_len=max_len)["tm"]
+    else:
+        score = lambda x, y, pp: tm_score(x, y, gen, gen, pp)["tm"]
+    tm = score(final["trans"], final["trans_1"], diag)
     aar = superpose(final["trans"], final["trans_1"], gen, gen, diag, aa_x=final["seqs"], aa_y=final["seqs_1"])["ident"]
     novel = (tm < novelty_tm) & (aar < novelty_ident)
 
@@ -148,7 +159,7 @@ def structure_scores(final, batch, groups=None, novelty_tm=0.5, novelty_ident=0.
 
     pairs, gidx, _ = group_pairs(labels)
     gidx = gidx.to(dev)
-    ptm = tm_score(final["trans"], final["trans"], gen, gen, pairs)["tm"]
+    ptm = score(final["trans"], final["trans"], pairs)
     npair = torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, torch.ones_like(gidx, dtype=torch.float64))
     div_tm = 1.0 - torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, ptm.double()) / npair
     return {"tm": tm, "tm_pooled": tm.double().mean(), "novel": novel, "novelty": novelty, "diversity_tm": div_tm,

@@ -5,7 +5,10 @@ batch_align at B = 64, L = 128, A = 15.  TM-score (pf_tm_score_fwd): pairwise at
 x 64 x 25 (32 256 pairs) and 64 sample-vs-native pairs at N = 128, checked against the float64 oracle of tests/tm_oracle.py on the
 CPU (a subset of the pairs; its time per pair is reported).  DSSP (pf_dssp_fwd): 4 096 chains x 25 residues (64 complexes x 64
 samples), 64 x 128 and 8 x 512 NeRF chains, checked against the float64 oracle of tests/dssp_oracle.py on a subset of the chains (its
-CPU time per chain is reported), and metrics.secondary_structure at 64 samples x 25 generated residues.  Per case: `call` = device events around REPS back-to-back calls of the Python function
+CPU time per chain is reported), and metrics.secondary_structure at 64 samples x 25 generated residues.  TM-align (pf_tm_align_fwd):
+pairwise at 64 samples x 25 CA (2 016 pairs), the same peptides inside 128-slot complex tensors (as structure_scores passes them),
+16 groups x 64 x 25 (32 256 pairs) and 64 sample-vs-native pairs at N = 128 with unequal lengths, checked against the float64 oracle
+of tests/tmalign_oracle.py on a subset (its CPU time per pair is reported).  Per case: `call` = device events around REPS back-to-back calls of the Python function
 (host overhead included), `graph` = the same calls captured once as a graph and replayed (device time per call; HIP only).  Prints one JSON
 line.  Usage: python tools/eval_bench.py [--reps 200]"""
 import argparse
@@ -23,6 +26,7 @@ from pepflowww_amd import _capi, geometry, metrics, synth  # noqa: E402
 import dssp_build  # noqa: E402
 import dssp_oracle  # noqa: E402
 import tm_oracle  # noqa: E402
+import tmalign_oracle  # noqa: E402
 
 
 def torch_pairwise(x, m, pairs):
@@ -109,6 +113,24 @@ def tm_case(x, y, m, pairs, reps, n_check):
             "oracle_cpu_ms_per_pair": round(per_pair * 1e3, 2)}
 
 
+def tmalign_case(x, y, mx, my, pairs, reps, n_check):
+    """pf_tm_align_fwd on the pair list (max_len = the longest chain, as structure_scores passes it), timed, and checked against
+    the float64 oracle on n_check pairs spread over the list"""
+    max_len = int(torch.maximum(mx.sum(1).max(), my.sum(1).max()))
+    out = geometry.tm_align(x, y, mx, my, pairs, alignment=True, max_len=max_len)
+    tm, y2x = out["tm"].cpu().double().numpy(), out["y2x"].cpu().numpy()
+    xs, ys, mxs, mys, pp = x.cpu().numpy(), y.cpu().numpy(), mx.cpu().numpy(), my.cpu().numpy(), pairs.cpu().numpy()
+    pick = np.linspace(0, len(pp) - 1, n_check).astype(int)
+    t0 = time.perf_counter()
+    ref = [tmalign_oracle.tm_align(xs[pp[q, 0]], ys[pp[q, 1]], mxs[pp[q, 0]], mys[pp[q, 1]]) for q in pick]
+    per_pair = (time.perf_counter() - t0) / n_check
+    return {"pairs": int(pairs.shape[0]), "N": int(x.shape[1]), "max_len": max_len, "checked": n_check,
+            "max_abs_diff_tm": float(max(abs(tm[q] - r["tm"]) for q, r in zip(pick, ref))),
+            "map_mismatches": int(sum(not np.array_equal(y2x[q], r["y2x"]) for q, r in zip(pick, ref))),
+            "hip": timed(lambda: geometry.tm_align(x, y, mx, my, pairs, max_len=max_len), reps),
+            "oracle_cpu_ms_per_pair": round(per_pair * 1e3, 1)}
+
+
 def dssp_chains(n_native, n_samples, n, seed):
     """n_native NeRF chains of n residues (phi / psi per segment from the helix, strand and coil basins), each repeated n_samples
     times with 0.3 A of noise -> pos [n_native * n_samples, n, 4, 3] on the device"""
@@ -168,6 +190,23 @@ def main():
     ids = torch.arange(64, dtype=torch.int32, device=dev)
     out["tm_native_64x128"] = tm_case(sample, native.contiguous(), torch.ones(64, 128, dtype=torch.bool, device=dev),
                                       torch.stack([ids, ids], 1), args.reps, 8)
+    ta_reps = max(args.reps // 10, 5)
+    for name, G in (("tmalign_pairwise_64x25", 1), ("tmalign_pairwise_16x64x25", 16)):
+        x = pocket_cas(G, 64, 200, 25)
+        m = torch.ones(x.shape[:2], dtype=torch.bool, device=dev)
+        pairs, _, _ = geometry.group_pairs(torch.arange(G).repeat_interleave(64))
+        out[name] = tmalign_case(x, x, m, m, pairs.to(dev), ta_reps, 16)
+    x25 = pocket_cas(1, 64, 200, 25)
+    cplx = torch.randn(64, 128, 3, generator=torch.Generator().manual_seed(6)).cuda() * 10.0
+    cplx[:, 40:65] = x25
+    m = torch.zeros(64, 128, dtype=torch.bool, device=dev)
+    m[:, 40:65] = True
+    pairs, _, _ = geometry.group_pairs(torch.zeros(64, dtype=torch.int64))
+    out["tmalign_pairwise_64x25_in128"] = tmalign_case(cplx, cplx, m, m, pairs.to(dev), ta_reps, 8)
+    keep = torch.rand(64, 128, generator=torch.Generator().manual_seed(7)).cuda() > 0.15
+    out["tmalign_native_64x128"] = tmalign_case(sample, native.contiguous(), keep,
+                                                torch.ones(64, 128, dtype=torch.bool, device=dev), torch.stack([ids, ids], 1),
+                                                ta_reps, 4)
     out["dssp_4096x25"] = dssp_case(dssp_chains(64, 64, 25, 400), args.reps, 64)
     out["dssp_64x128"] = dssp_case(dssp_chains(64, 1, 128, 401), args.reps, 16)
     out["dssp_8x512"] = dssp_case(dssp_chains(8, 1, 512, 402), args.reps, 4)
