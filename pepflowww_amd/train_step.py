@@ -101,9 +101,14 @@ class GraphedTrainStep:
         step = GraphedTrainStep(model, batch, loss_weights)       # captures (same B, L for every later batch)
         losses = step(batch, noise=None)                          # replay; model.parameters() have .grad set
         optimizer.step()
+
+    Nothing of the capture depends on the contents of the first batch: masks, lengths and noise are read from the static buffers by
+    every replay, so a later batch may be padded differently.  The two categorical draws of the step come from the device Philox
+    stream (`seed`) unless the step was captured with given_draws=True: then every replay reads them from noise['expo'] [2,B,L,20]
+    (parity tests replay the oracle's draws this way).  A replay whose noise does not match the captured form is refused.
     """
 
-    def __init__(self, model, batch, loss_weights, first_sample=0, generator=None):
+    def __init__(self, model, batch, loss_weights, first_sample=0, generator=None, given_draws=False):
         _capi.load()
         for n, p in model.named_parameters():
             if p.dtype != torch.float32 or not p.is_contiguous():
@@ -115,6 +120,9 @@ class GraphedTrainStep:
         self.batch = {k: v.clone() for k, v in batch.items() if torch.is_tensor(v)}
         nz = default_train_noise(B, L, generator)
         self.noise = {k: v.to(dev, torch.float32).contiguous() for k, v in nz.items()}
+        self.given_draws = bool(given_draws)
+        if self.given_draws:                              # static buffer of the Exp(1) draws (1.0 keeps p / E finite during the warm-up)
+            self.noise["expo"] = torch.full((2, B, L, 20), 1.0, dtype=torch.float32, device=dev)
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
         self.weights = torch.tensor([float(loss_weights[k]) for k in LOSS_KEYS], dtype=torch.float32, device=dev)
         self.names, sd = _state_dict_f32(model)
@@ -150,8 +158,15 @@ class GraphedTrainStep:
     def __call__(self, batch=None, noise=None, seed=None):
         """Refresh the static inputs (given ones only), replay, -> dict of the six losses (views of a static tensor)."""
         if batch is not None:
+            if tuple(batch["aa"].shape) != (self.B, self.L):
+                raise ValueError(f"GraphedTrainStep was captured at (B, L) = {(self.B, self.L)}: got a batch of {tuple(batch['aa'].shape)}")
             for k, v in self.batch.items():
                 v.copy_(batch[k])
+        has_expo = noise is not None and noise.get("expo") is not None
+        if has_expo != self.given_draws:                  # (never silently ignore given draws, never replay stale ones)
+            raise ValueError("GraphedTrainStep captured with given_draws=True reads the categorical draws from noise['expo'] at every replay"
+                             if self.given_draws else
+                             "noise['expo'] given, but this step was captured with device Philox draws: capture with given_draws=True")
         nz = default_train_noise(self.B, self.L, self.generator) if noise is None else noise
         for k, v in self.noise.items():
             v.copy_(nz[k].reshape(v.shape))

@@ -110,7 +110,7 @@ def test_cfg4_twenty_free_steps_vs_oracle(model, seeded_sd):
 def test_cfg5_training_step_vs_oracle_autograd(seeded_sd):
     """B=16 x L=128 training step (default path: fused EdgeTransition forward, mid-size attention variant): losses and
     the gradient tensor of all 407 parameters against the oracle's autograd."""
-    from test_oracle_golden import oracle_param_grads
+    import train_oracle as T
     B, L = 16, 128
     batch = synth.make_pocket_batch(B, L, 16, seed=2024)
     nz = synth.make_noise(B, L, 1, seed=5)
@@ -118,64 +118,22 @@ def test_cfg5_training_step_vs_oracle_autograd(seeded_sd):
              "ang0": nz["ang0"], "simplex0": nz["simplex0"], "expo": nz["expo"][:2].clone()}
     # keep every categorical draw away from its decision boundary (a flipped residue type changes the torsion mask of the
     # angle losses -- a discontinuity no tolerance covers): widen draws whose top-2 gap is < 5 % on the oracle's forward
-    with torch.no_grad():
-        enc = O.encode(seeded_sd, batch)
-        for _ in range(3):
-            state = O.corrupt(batch, enc, noise)
-            preds = O.ga_encoder(seeded_sd, *state, enc[4], enc[5], batch["res_mask"].long())
-            sx = torch.where(batch["generate_mask"][..., None], (1 - state[0][..., None]) * (5.0 * noise["simplex0"]) +
-                             state[0][..., None] * O.seq_to_simplex(enc[3]), O.seq_to_simplex(enc[3]))
-            changed = 0
-            for d, p in ((0, torch.softmax(sx, -1)), (1, torch.softmax(preds[3], -1))):
-                sc = (p + 1e-8) / noise["expo"][d]
-                top = torch.topk(sc, 2, dim=-1)
-                tight = (1 - top.values[..., 1] / top.values[..., 0]) < 0.05
-                if tight.any():
-                    idx = top.indices[..., 0][tight]
-                    e = noise["expo"][d][tight]
-                    e[torch.arange(e.shape[0]), idx] *= 0.5          # the winner wins by more
-                    noise["expo"][d][tight] = e
-                    changed += int(tight.sum())
-            if not changed:
-                break
-    ref_g, ref_l = oracle_param_grads(seeded_sd, batch, noise)
+    T.widen_draws(seeded_sd, batch, noise, rounds=3, gen_only=False)
+    # tolerance: the oracle's own fp32 gradient is noisy on the parameters whose gradient is a long cancelling sum over all
+    # B*L*L pairs (golden F6 'param_fp32_noise': encoder distance MLP 2-5e-2, everything else <= 5e-3): measured against
+    # the same step in float64 on the oracle, per parameter (tests/train_oracle.py: oracle_truth, compare)
+    g64, ref_g, ref_l = T.oracle_truth(seeded_sd, batch, noise)
     m = pepflowww_amd.FlowModel(pepflowww_amd.default_config())
     m.load_state_dict(seeded_sd, strict=True)
     m = m.to(G.dev()).train()
     ld = m({k: cu(v) for k, v in batch.items()}, noise=noise)
-    for k, v in ld.items():
-        assert abs(v.item() - ref_l[k].item()) <= REL * abs(ref_l[k].item()), (k, v.item(), ref_l[k].item())
+    assert T.REL_LOSS == REL
+    T.check_losses({k: v.item() for k, v in ld.items()}, ref_l)                  # against the oracle's fp32 losses
     sum(O.LOSS_WEIGHTS[k] * v for k, v in ld.items()).backward()
     G.sync()
-    # tolerance: the oracle's own fp32 gradient is noisy on the parameters whose gradient is a long cancelling sum over all
-    # B*L*L pairs (golden F6 'param_fp32_noise': encoder distance MLP 2-5e-2, everything else <= 5e-3): measured against
-    # the same step in float64 on the oracle, per parameter, here
-    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in seeded_sd.items()}
-    b64 = {k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in batch.items()}
-    n64 = {k: v.double() for k, v in noise.items()}
-    keep = O.BB_IDEAL
-    O.BB_IDEAL = O.BB_IDEAL.double()
-    try:
-        g64, _ = oracle_param_grads(sd64, b64, n64)
-    finally:
-        O.BB_IDEAL = keep
-    bad, worst = [], (0.0, None)
-    for name, p in m.named_parameters():
-        g, r, r64 = p.grad.detach().float().cpu(), ref_g[name], g64[name]
-        assert g.shape == r.shape, name
-        if name.endswith("linear_b.bias"):
-            assert g.abs().max() < 5e-5, name
-            continue
-        scale = r64.abs().max().clamp_min(1e-12)
-        noise_lvl = ((r.double() - r64).abs().max() / scale).item()
-        err = ((g.double() - r64).abs().max() / scale).item()            # against the float64 truth
-        tol = 3e-4 + 3 * noise_lvl
-        if err / tol > worst[0]:
-            worst = (err / tol, name, err, noise_lvl)
-        if err > tol:
-            bad.append((name, err, noise_lvl))
-    print("cfg5 gradients vs float64 oracle, worst err/tol:", worst)
-    assert not bad, (len(bad), bad[:8])
+    r = T.compare({name: p.grad for name, p in m.named_parameters()}, g64, ref_g, strict=False)
+    print("cfg5 gradients vs float64 oracle, worst err/tol:", r["worst"])
+    assert not r["bad"], (len(r["bad"]), r["bad"][:8])
 
 
 def test_cfg3_variable_length_batch(model, seeded_sd):
