@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PF_ABI_VERSION 63
+#define PF_ABI_VERSION 64
 #define PF_ATT_VROWS 164             /* rows of a head's transposed value block: 128 channels + 12 points x 3 */
 /* att_vt (f16 mode, ABI 53): a head's transposed values [PF_ATT_VROWS rows][keys] in the FRAGMENT ORDER of the score kernel's second
  * product -- block (tile n, 32-key step) = 512 f16 = the eight operand slots of each of its 64 lanes: row c sits in tile n = c & 7 as
@@ -921,6 +921,46 @@ typedef struct {
 } pf_tm_align_args;
 int pf_tm_align_fwd(const pf_tm_align_args* a, pf_stream_t stream);
 int pf_tm_align_lds_bytes(int max_len);        /* dynamic LDS of one pair's workgroup (0 for max_len outside [1, PF_TM_ALIGN_MAX_N]) */
+
+/* ---- structural violations (ABI 64) ---------------------------------------------------------------------------------------
+ * pf_violations_fwd: AlphaFold's between-residue structural violations (Jumper et al. 2021, Suppl. 1.9.11) of B structures of N
+ * residues, with the values of OpenFold's between_residue_clash_loss, between_residue_bond_loss and
+ * extreme_ca_ca_distance_violations (openfold/utils/loss.py); the conventions are listed in csrc/violations.hip.
+ * pos [B,N,n_atoms,3] in the package's heavy-atom order, n_atoms >= 14, only slots 0..13 are read (pos_heavyatom passes as it is);
+ * atom_mask [B,N,n_atoms]; aa [B,N] in the package's numbering; residue_index [B,N]; radius [21,14] van der Waals radii by
+ * (type, slot), 0 where the type has no such atom; query [B,N] optional: only atom pairs with an atom in a query residue are
+ * evaluated; group [B,N] optional: needed by the *_cross outputs.
+ *   clash_atom_loss [B,N,14]   sum of relu(r_a + r_b - clash_overlap_tolerance - d) over the atom's counted partners;
+ *   clash_atom [B,N,14]        1 where some counted partner is closer than r_a + r_b - clash_overlap_tolerance;
+ *   clash_atom_pairs [B,N,14]  counted partners of the atom;
+ *   clash_atom_loss_cross, clash_atom_cross [B,N,14]  the same over partners of another group (optional, both or neither);
+ *   clash_mean_loss [B]        summed loss of the unordered pairs / (1e-6 + their number);
+ *   bond_c_n_loss_mean, angle_ca_c_n_loss_mean, angle_c_n_ca_loss_mean [B]  masked means over the connections (n, n + 1);
+ *   connection_loss [B,N]      half the loss of connection n - 1 plus half that of connection n (not masked, as the reference);
+ *   connection_violation [B,N] 1 where connection n - 1 or n violates a bound by more than violation_tolerance_factor stddev;
+ *   ca_ca_break [B,N]          1 where CA(n) - CA(n + 1) exceeds 3.802 + 1.5 A (connection n, stored at n);
+ *   ca_ca_extreme [B]          breaks / (1e-4 + connections tested).
+ * A connection is tested where residue_index[n + 1] - residue_index[n] == 1 and its atoms exist.  The CA-C-N angle test uses the
+ * bond-length stddev 0.014 (loss.py:807).  Two launches, no atomics, no scratch, no host synchronisation; memory is O(B N).
+ * Results are bit-identical from run to run and do not depend on the other samples.  B > 65535 -> PF_E_TOOLARGE. */
+typedef struct {
+    const float* pos;                   /* [B,N,n_atoms,3] */
+    const unsigned char* atom_mask;     /* [B,N,n_atoms] */
+    const int64_t* aa;                  /* [B,N] */
+    const int* residue_index;           /* [B,N] */
+    const unsigned char* query;         /* [B,N] optional */
+    const unsigned char* group;         /* [B,N] optional */
+    const float* radius;                /* [21,14] */
+    float* clash_atom_loss; unsigned char* clash_atom; int* clash_atom_pairs;       /* [B,N,14] */
+    float* clash_atom_loss_cross; unsigned char* clash_atom_cross;                  /* [B,N,14] optional */
+    float* clash_mean_loss;                                                         /* [B] */
+    float* bond_c_n_loss_mean; float* angle_ca_c_n_loss_mean; float* angle_c_n_ca_loss_mean;   /* [B] */
+    float* connection_loss; unsigned char* connection_violation; unsigned char* ca_ca_break;    /* [B,N] */
+    float* ca_ca_extreme;                                                           /* [B] */
+    int B, N, n_atoms, pro;             /* pro: the residue index of proline */
+    float violation_tolerance_factor, clash_overlap_tolerance;      /* AlphaFold: 12.0, 1.5 */
+} pf_violations_args;
+int pf_violations_fwd(const pf_violations_args* a, pf_stream_t stream);
 
 #ifdef __cplusplus
 }

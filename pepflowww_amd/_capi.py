@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (PF_LIB_PATH: another build of the same library -- same-box A/B runs of kernel variants, tools/dev)
 LIB_PATH = os.environ.get("PF_LIB_PATH") or os.path.join(_HERE, "lib", "libpepflow_hip.so")
-ABI_VERSION = 63
+ABI_VERSION = 64
 
 _fp = C.c_void_p
 _i = C.c_int
@@ -195,6 +195,15 @@ class TmAlignArgs(C.Structure):
                 ("aligned", _fp), ("Bx", _i), ("By", _i), ("N", _i), ("P", _i), ("max_len", _i)]
 
 
+class ViolationsArgs(C.Structure):
+    _fields_ = [("pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("residue_index", _fp), ("query", _fp), ("group", _fp), ("radius", _fp),
+                ("clash_atom_loss", _fp), ("clash_atom", _fp), ("clash_atom_pairs", _fp), ("clash_atom_loss_cross", _fp),
+                ("clash_atom_cross", _fp), ("clash_mean_loss", _fp), ("bond_c_n_loss_mean", _fp), ("angle_ca_c_n_loss_mean", _fp),
+                ("angle_c_n_ca_loss_mean", _fp), ("connection_loss", _fp), ("connection_violation", _fp), ("ca_ca_break", _fp),
+                ("ca_ca_extreme", _fp), ("B", _i), ("N", _i), ("n_atoms", _i), ("pro", _i),
+                ("violation_tolerance_factor", C.c_float), ("clash_overlap_tolerance", C.c_float)]
+
+
 class EtBwdArgs(C.Structure):
     _fields_ = [("g_y", _fp), ("h1", _fp), ("h2", _fp), ("wfT_f16", _fp), ("w2T_f16", _fp), ("w1T_f16", _fp),
                 ("g_h2", _fp), ("g_h1", _fp), ("g_x", _fp), ("npairs", C.c_longlong), ("m1", _fp), ("m2", _fp)]
@@ -275,6 +284,7 @@ _SIGNATURES = {
     "pf_dssp_fwd": ([C.POINTER(DsspArgs), _fp], _i),
     "pf_tm_align_fwd": ([C.POINTER(TmAlignArgs), _fp], _i),
     "pf_tm_align_lds_bytes": ([_i], _i),
+    "pf_violations_fwd": ([C.POINTER(ViolationsArgs), _fp], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -2,7 +2,8 @@
 reference's sampling drivers), Kabsch RMSD and the pairwise RMSD / sequence-identity matrix of a set of samples, on the HIP kernel
 pf_superpose_fwd (one wave per pair of a work list, fp64 sums and 3x3 SVD); TM-score with a fixed residue correspondence and its
 pairwise matrix on pf_tm_score_fwd (one lane per seed of the TMscore program's search); DSSP secondary structure on pf_dssp_fwd
-(one workgroup per chain slot).
+(one workgroup per chain slot); AlphaFold's between-residue structural violations (clashes, peptide-bond geometry, CA-CA breaks) on
+pf_violations_fwd (tiled all-pairs pass over the heavy atoms, nothing pair-sized in memory).
 
 Deviation from the reference: `batch_align` selects each sample's masked atoms on their own.  The reference's
 `masked_select(...).reshape(B, -1, 3)` mixes atoms across samples when the per-sample mask counts differ; where the counts are equal
@@ -347,3 +348,88 @@ def ss_strings(ss, simplified=False):
         sym = SS_SYMBOLS
     rows = ss.reshape(-1, ss.shape[-1]).cpu().tolist()
     return ["".join(sym[c] for c in row if c < len(sym)) for row in rows]
+
+
+VDW_RADIUS = {"C": 1.7, "N": 1.55, "O": 1.52, "S": 1.8}    # openfold/np/residue_constants.py van_der_waals_radius
+VIOLATION_SLOTS = 14
+_UNK_ELEMENTS = "NCCO"          # a residue type >= 20: N, CA, C, O only
+_RADIUS = {}
+
+
+def vdw_radius_table():
+    """-> [21,14] float32 CPU tensor: the van der Waals radius of heavy-atom slot s of residue type t (the package's numbering),
+    from the first letter of the slot's atom name in the package's own table (data/rigid_groups.npz); 0 where the type has no
+    such atom.  Row 20 (any type outside 0..19) has N, CA, C, O."""
+    from .preprocess import _tables
+    names = _tables()["atom_names"]
+    tab = torch.zeros(21, VIOLATION_SLOTS)
+    for t in range(20):
+        for s in range(VIOLATION_SLOTS):
+            if names[t][s]:
+                tab[t, s] = VDW_RADIUS[names[t][s][0]]
+    for s, e in enumerate(_UNK_ELEMENTS):
+        tab[20, s] = VDW_RADIUS[e]
+    return tab
+
+
+def structural_violations(pos, atom_mask, aa, residue_index, query=None, group=None, violation_tolerance_factor=12.0,
+                          clash_overlap_tolerance=1.5):
+    """pf_violations_fwd: AlphaFold's between-residue structural violations (Jumper et al. 2021, Suppl. 1.9.11) with the values of
+    OpenFold's between_residue_clash_loss, between_residue_bond_loss and extreme_ca_ca_distance_violations (conventions:
+    csrc/violations.hip).
+
+    pos [B,N,A,3] heavy atoms in the package's order, A >= 14, slots 0..13 are read (pos_heavyatom passes as it is); atom_mask
+    [B,N,A]; aa [B,N] residue types in the package's numbering; residue_index [B,N] integers: a peptide bond is tested between n
+    and n + 1 where it grows by exactly 1, and residues of equal index are never compared for clashes; query [B,N] (optional): only
+    atom pairs with an atom in a query residue are evaluated; group [B,N] (optional): adds the *_cross outputs, over partners of
+    another group.
+    -> dict of device tensors: clash_atom_loss [B,N,14] float32, clash_atom [B,N,14] bool, clash_atom_pairs [B,N,14] int32,
+    clash_mean_loss [B]; with `group` clash_atom_loss_cross, clash_atom_cross; bond_c_n_loss_mean, angle_ca_c_n_loss_mean,
+    angle_c_n_ca_loss_mean [B]; connection_loss [B,N]; connection_violation [B,N] bool; ca_ca_break [B,N] bool (connection
+    (n, n + 1) at n); ca_ca_extreme [B]."""
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 4 or pos.shape[3] != 3 or pos.shape[2] < VIOLATION_SLOTS:
+        raise ValueError(f"pos must be [B,N,A,3] with A >= {VIOLATION_SLOTS}, got {tuple(getattr(pos, 'shape', ()))}")
+    B, N, A, _ = pos.shape
+    if tuple(atom_mask.shape) != (B, N, A):
+        raise ValueError(f"atom_mask must be [B,N,A] = {(B, N, A)}, got {tuple(atom_mask.shape)}")
+    for nm, t in (("aa", aa), ("residue_index", residue_index), ("query", query), ("group", group)):
+        if t is not None and tuple(t.shape) != (B, N):
+            raise ValueError(f"{nm} must be [B,N] = {(B, N)}, got {tuple(t.shape)}")
+    dev = pos.device
+    key = str(dev)
+    keep = [pos.to(dev, torch.float32).contiguous(), atom_mask.to(dev).to(torch.uint8).contiguous(),
+            aa.to(dev, torch.int64).contiguous(), residue_index.to(dev, torch.int32).contiguous()]
+    a = _capi.ViolationsArgs()
+    a.pos, a.atom_mask = _capi.dptr(keep[0], torch.float32, "pos"), _capi.dptr(keep[1], torch.uint8, "atom_mask")
+    a.aa, a.residue_index = _capi.dptr(keep[2], torch.int64, "aa"), _capi.dptr(keep[3], torch.int32, "residue_index")
+    if key not in _RADIUS:
+        _RADIUS[key] = vdw_radius_table().contiguous().to(dev)
+    a.radius = _RADIUS[key].data_ptr()
+    if query is not None:
+        keep.append(_u8(query, (B, N), dev))
+        a.query = keep[-1].data_ptr()
+    if group is not None:
+        keep.append(_u8(group, (B, N), dev))
+        a.group = keep[-1].data_ptr()
+    S = VIOLATION_SLOTS
+    f32 = lambda *shape: torch.empty(*shape, device=dev)  # noqa: E731
+    u8 = lambda *shape: torch.empty(*shape, dtype=torch.uint8, device=dev)  # noqa: E731
+    out = {"clash_atom_loss": f32(B, N, S), "clash_atom": u8(B, N, S),
+           "clash_atom_pairs": torch.empty(B, N, S, dtype=torch.int32, device=dev), "clash_mean_loss": f32(B)}
+    if group is not None:
+        out.update(clash_atom_loss_cross=f32(B, N, S), clash_atom_cross=u8(B, N, S))
+    out.update(bond_c_n_loss_mean=f32(B), angle_ca_c_n_loss_mean=f32(B), angle_c_n_ca_loss_mean=f32(B), connection_loss=f32(B, N),
+               connection_violation=u8(B, N), ca_ca_break=u8(B, N), ca_ca_extreme=f32(B))
+    for k, v in out.items():
+        setattr(a, k, v.data_ptr())
+    a.B, a.N, a.n_atoms, a.pro = B, N, A, _proline()
+    a.violation_tolerance_factor, a.clash_overlap_tolerance = float(violation_tolerance_factor), float(clash_overlap_tolerance)
+    if B and N:
+        _capi.check(_capi.load().pf_violations_fwd(C.byref(a), _capi.stream_ptr()), "pf_violations_fwd")
+    else:
+        for v in out.values():
+            v.zero_()
+    for k in ("clash_atom", "clash_atom_cross", "connection_violation", "ca_ca_break"):
+        if k in out:
+            out[k] = out[k].bool()
+    return out

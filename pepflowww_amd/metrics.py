@@ -3,16 +3,18 @@
 CA RMSD after superposition, `get_rmsd` 47-59; binding-site ratio, `get_bind_site` / `get_bind_ratio` 93-110; diversity among the
 samples of one complex), without Biopython / tmtools / mdtraj and without writing PDB files; TM-score against the native, novelty
 and TM-score diversity (`structure_scores`); DSSP secondary structure and the secondary-structure ratio, `get_second_stru` / `get_ss`
-79-91 (`secondary_structure`).
+79-91 (`secondary_structure`); clashes and broken peptide bonds, AlphaFold's between-residue structural violations
+(`structural_violations`).
 
-Every per-residue and per-point operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd (and the
-backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
+Every per-residue, per-point and per-atom-pair operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd /
+pf_violations_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
 import torch
 
 from . import _capi, full_atom
+from . import geometry
 from .geometry import dssp, group_pairs, ss_simplify, superpose, tm_align, tm_score
 
 BIND_CUTOFF = 10.0          # eval/geometry.py:100: receptor residues within 10 A of a peptide CA
@@ -202,3 +204,74 @@ def secondary_structure(final, batch, backbone="full_atom"):
     pooled = torch.nan_to_num(ssr).sum() / (n > 0).sum()
     return {"ss_sample": ss_s, "ss_native": ss_n, "ssr": ssr, "ssr_pooled": pooled,
             "helix": frac[0], "strand": frac[1], "coil": frac[2]}
+
+
+def residue_index(chain_nb, res_nb, res_mask):
+    """-> [B,L] int32: 0 at the first residue, + 1 for a step to the next residue of the same chain (both in res_mask, res_nb
+    growing by 1), + 2 for any other step.  Indices are unique and increasing, and grow by exactly 1 between bonded neighbours only."""
+    ok = res_mask.bool()
+    bonded = (chain_nb[:, 1:] == chain_nb[:, :-1]) & (res_nb[:, 1:] - res_nb[:, :-1] == 1) & ok[:, 1:] & ok[:, :-1]
+    step = torch.where(bonded, 1, 2).to(torch.int32)
+    return torch.cat([torch.zeros_like(step[:, :1]), torch.cumsum(step, 1, dtype=torch.int32)], 1)
+
+
+def structural_violations(final, batch, backbone="full_atom", scope="generated"):
+    """Clashes and broken peptide bonds of each sample's complex and of its native: AlphaFold's between-residue structural
+    violations (geometry.structural_violations; the within-residue part is left out).  final / batch as in `evaluate_samples`
+    (batch also chain_nb, res_nb).
+
+    backbone: "full_atom" -- generated residues rebuilt with all heavy atoms (reconstruct_sample: rotmats, trans, angles, seqs), the
+    context kept; "frames" -- generated residues rebuilt as N, CA, C, O (reconstruct_sample_bb).  The native complex is pos_heavyatom /
+    mask_heavyatom / seqs_1.  residue_index comes from `residue_index`, group = generate_mask.
+    scope: "generated" -- only atom pairs with an atom in a generated residue are evaluated (query = generate_mask); "all" -- every
+    pair, so context residues clashing with each other show in the per-atom arrays too.
+
+    -> dict of device tensors.  Per sample [B], fractions of the generated residues (NaN for a sample without any):
+      bond_violation   a peptide bond or bond angle to a neighbour off by more than 12 standard deviations;
+      ca_ca_break      CA more than 3.80 + 1.5 A from the next residue's CA;
+      clash            an atom overlapping an atom of another residue by more than 1.5 A;
+      clash_receptor   such an overlap with an atom of a context residue;  clash_internal  with one of another generated residue;
+      violation        any of bond_violation / clash (the reference's violations_per_residue without the within-residue term);
+    valid [B] bool: no generated residue has a violation or a CA-CA break; valid_fraction: the mean of valid over the samples that
+    have generated residues (float64 scalar); n_clashing_atoms [B] clashing atoms of generated residues.  The same keys with
+    `_native` appended for the native complex.  Arrays of the sample (and `*_native`): residue_bond_violation, residue_ca_ca_break,
+    residue_clash [B,L] bool, atom_clash, atom_clash_receptor [B,L,14] bool, atom_clash_loss [B,L,14]; residue_index [B,L]."""
+    if backbone not in ("full_atom", "frames"):
+        raise ValueError(f"backbone must be 'full_atom' or 'frames', got {backbone!r}")
+    if scope not in ("generated", "all"):
+        raise ValueError(f"scope must be 'generated' or 'all', got {scope!r}")
+    dev = _device(batch["generate_mask"], final["trans"], batch["pos_heavyatom"])
+    res_mask = batch["res_mask"].to(dev).bool()
+    gen = batch["generate_mask"].to(dev).bool() & res_mask
+    rotmats, trans, seqs = (final[k].to(dev) for k in ("rotmats", "trans", "seqs"))
+    pos_n, mask_n = batch["pos_heavyatom"].to(dev), batch["mask_heavyatom"].to(dev).bool()
+    chain_nb, res_nb = batch["chain_nb"].to(dev), batch["res_nb"].to(dev)
+    if backbone == "full_atom":
+        pos_s, mask_s = full_atom.reconstruct_sample(rotmats, trans, final["angles"].to(dev), seqs, gen, pos_n)
+        mask_s = torch.where(gen[:, :, None], mask_s, mask_n[:, :, :15])
+    else:
+        pos_s, mask_s = full_atom.reconstruct_sample_bb(rotmats, trans, seqs, chain_nb, res_nb, res_mask, gen, pos_n, mask_n)
+    index = residue_index(chain_nb, res_nb, res_mask)
+    query = gen if scope == "generated" else None
+    aa_s = torch.where(gen, seqs, final["seqs_1"].to(dev))
+    n = gen.sum(1).double()
+    has = n > 0
+    out = {"residue_index": index}
+    for tag, pos, mask, aa in (("", pos_s, mask_s, aa_s), ("_native", pos_n, mask_n, final["seqs_1"].to(dev))):
+        v = geometry.structural_violations(pos, mask & res_mask[:, :, None], aa, index, query=query, group=gen)
+        bond, brk = v["connection_violation"], v["ca_ca_break"]
+        brk = brk | torch.nn.functional.pad(brk[:, :-1], (1, 0))           # a break counts for both of its residues
+        clash, cross = v["clash_atom"].any(-1), v["clash_atom_cross"].any(-1)
+        # the generated residues on their own: every partner is generated
+        inner = geometry.structural_violations(pos, mask & gen[:, :, None], aa, index)["clash_atom"].any(-1)
+        frac = lambda m: torch.where(has, (m & gen).sum(1).double() / n, torch.full_like(n, float("nan")))  # noqa: E731
+        any_v = bond | clash
+        valid = ~((any_v | brk) & gen).any(1)
+        res = {"bond_violation": frac(bond), "ca_ca_break": frac(brk), "clash": frac(clash), "clash_receptor": frac(cross),
+               "clash_internal": frac(inner), "violation": frac(any_v), "valid": valid,
+               "valid_fraction": (valid & has).sum().double() / has.sum(),
+               "n_clashing_atoms": (v["clash_atom"] & gen[:, :, None]).sum((1, 2)),
+               "residue_bond_violation": bond, "residue_ca_ca_break": brk, "residue_clash": clash, "atom_clash": v["clash_atom"],
+               "atom_clash_receptor": v["clash_atom_cross"], "atom_clash_loss": v["clash_atom_loss"]}
+        out.update({k + tag: t for k, t in res.items()})
+    return out

@@ -8,9 +8,12 @@ samples), 64 x 128 and 8 x 512 NeRF chains, checked against the float64 oracle o
 CPU time per chain is reported), and metrics.secondary_structure at 64 samples x 25 generated residues.  TM-align (pf_tm_align_fwd):
 pairwise at 64 samples x 25 CA (2 016 pairs), the same peptides inside 128-slot complex tensors (as structure_scores passes them),
 16 groups x 64 x 25 (32 256 pairs) and 64 sample-vs-native pairs at N = 128 with unequal lengths, checked against the float64 oracle
-of tests/tmalign_oracle.py on a subset (its CPU time per pair is reported).  Per case: `call` = device events around REPS back-to-back calls of the Python function
+of tests/tmalign_oracle.py on a subset (its CPU time per pair is reported).  Structural violations (pf_violations_fwd, `--only
+violations` runs this leg alone): the heavy atoms of 64 complexes of 144 and of 512 residues, every pair and with query = the 12
+generated residues, against a dense torch restatement of the clash pass ([B,L,L,14,14] tensors) on the device at 8 x 144, and
+metrics.structural_violations at 64 x 144.  Per case: `call` = device events around REPS back-to-back calls of the Python function
 (host overhead included), `graph` = the same calls captured once as a graph and replayed (device time per call; HIP only).  Prints one JSON
-line.  Usage: python tools/eval_bench.py [--reps 200]"""
+line.  Usage: python tools/eval_bench.py [--reps 200] [--only violations]"""
 import argparse
 import json
 import os
@@ -153,13 +156,62 @@ def dssp_case(pos, reps, n_check):
             "hip": timed(lambda: geometry.dssp(pos, mask), reps), "oracle_cpu_ms_per_chain": round(per_chain * 1e3, 3)}
 
 
+def torch_dense_clashes(pos, exists, radius, index, tol=1.5):
+    """the clash pass written densely with torch ops, pair tensors [B,L,L,14,14] -> per-atom loss, per-atom flag, mean loss [B]"""
+    pos, exists = pos[:, :, :14], exists[:, :, :14]
+    d = torch.sqrt(1e-10 + ((pos[:, :, None, :, None] - pos[:, None, :, None, :]) ** 2).sum(-1))
+    m = exists[:, :, None, :, None] & exists[:, None, :, None, :] & (index[:, :, None] != index[:, None, :])[..., None, None]
+    s = torch.arange(14, device=pos.device)
+    cn = (index[:, :, None] + 1 == index[:, None, :])[..., None, None] & (s == 2)[:, None] & (s == 0)[None, :]
+    m = m & ~cn & ~cn.permute(0, 2, 1, 4, 3) & ~((s == 5)[:, None] & (s == 5)[None, :])
+    lim = radius[:, :, None, :, None] + radius[:, None, :, None, :] - tol
+    e = torch.where(m, torch.relu(lim - d), torch.zeros_like(d))
+    return e.sum((2, 4)), (m & (d < lim)).any(4).any(2), 0.5 * e.sum((1, 2, 3, 4)) / (1e-6 + 0.5 * m.sum((1, 2, 3, 4)))
+
+
+def violation_cases(reps):
+    out = {}
+    table = geometry.vdw_radius_table().cuda()
+    for L in (144, 512):
+        batch = {k: v.cuda() for k, v in synth.make_pocket_batch(64, L, 12, seed=500 + L).items()}
+        pos, mask, aa = batch["pos_heavyatom"], batch["mask_heavyatom"].to(torch.uint8), batch["aa"]
+        index = metrics.residue_index(batch["chain_nb"], batch["res_nb"], batch["res_mask"])
+        gen = batch["generate_mask"].to(torch.uint8)
+        v = geometry.structural_violations(pos, mask, aa, index, group=gen)
+        case = {"atoms": int(mask[:, :, :14].sum()), "atom_pairs_counted": int(v["clash_atom_pairs"].long().sum() // 2),
+                "clashing_atoms": int(v["clash_atom"].sum()),
+                "all_pairs": timed(lambda: geometry.structural_violations(pos, mask, aa, index), reps),
+                "all_pairs_group": timed(lambda: geometry.structural_violations(pos, mask, aa, index, group=gen), reps),
+                "query_generated": timed(lambda: geometry.structural_violations(pos, mask, aa, index, query=gen, group=gen), reps)}
+        if L == 144:
+            p8, m8, i8 = pos[:8], mask[:8].bool(), index[:8]
+            r8 = table[aa[:8].clamp(0, 20)] * m8[:, :, :14]
+            loss, flag, mean = torch_dense_clashes(p8, m8 & (torch.nn.functional.pad(table, (0, 1))[aa[:8].clamp(0, 20)] > 0), r8, i8)
+            case["dense_torch_8x144"] = {"max_abs_diff_loss": float((loss - v["clash_atom_loss"][:8]).abs().max()),
+                                         "flag_mismatches": int((flag != v["clash_atom"][:8]).sum()),
+                                         "max_abs_diff_mean": float((mean - v["clash_mean_loss"][:8]).abs().max()),
+                                         "hip_8x144": timed(lambda: geometry.structural_violations(p8, mask[:8], aa[:8], i8), reps),
+                                         "torch": timed(lambda: torch_dense_clashes(p8, m8, r8, i8), max(reps // 20, 3), graph=False)}
+            rot = torch.linalg.qr(torch.randn(64, L, 3, 3, generator=torch.Generator().manual_seed(505)))[0].cuda()
+            final = {"rotmats": rot, "trans": pos[:, :, 1].contiguous(), "angles": batch["torsion_angle"], "seqs": aa, "seqs_1": aa}
+            for bb in ("full_atom", "frames"):
+                case[f"metrics_{bb}"] = timed(lambda: metrics.structural_violations(final, batch, backbone=bb), max(reps // 4, 3), graph=False)
+        out[f"violations_64x{L}"] = case
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--only", choices=["violations"], default=None, help="run one leg alone")
     args = ap.parse_args()
     _capi.load()
     dev = torch.device("cuda")
     out = {"device": torch.cuda.get_device_name(0)}
+    if args.only == "violations":
+        out.update(violation_cases(args.reps))
+        print(json.dumps(out))
+        return
     for name, G in (("pairwise_64x25", 1), ("pairwise_16x64x25", 16)):
         x = pocket_cas(G, 64, 100)
         m = torch.ones(x.shape[:2], dtype=torch.bool, device=dev)
@@ -217,6 +269,7 @@ def main():
     for bb in ("full_atom", "frames"):
         out[f"secondary_structure_64x25_{bb}"] = {"hip": timed(lambda: metrics.secondary_structure(final, batch, backbone=bb),
                                                                args.reps, graph=False)}
+    out.update(violation_cases(args.reps))
     print(json.dumps(out))
 
 
