@@ -962,6 +962,40 @@ typedef struct {
 } pf_violations_args;
 int pf_violations_fwd(const pf_violations_args* a, pf_stream_t stream);
 
+/* ---- solvent-accessible surface area (ABI 64, added entry point) -------------------------------------------------------------
+ * pf_sasa_fwd: Shrake-Rupley solvent-accessible surface of B structures of N residues; the conventions are listed in
+ * csrc/sasa.hip.  pos [B,N,n_atoms,3] in the package's heavy-atom order, n_atoms >= 14, slots 0 .. min(n_atoms,15)-1 are read;
+ * atom_mask [B,N,n_atoms]; aa [B,N]; radius [21,15] by (type, slot), 0 where the type has no such atom; points [n_points,3] unit
+ * vectors, 1 <= n_points <= PF_SASA_MAX_POINTS; work [B,N,4] scratch (per-residue centre and padded extent); query [B,N] optional:
+ * only atoms of query residues are evaluated (every existing atom is still a partner); group [B,N] optional: needed by the *_own
+ * outputs (all four or none), the same quantities with only atoms of residues of the same group byte as partners.
+ *   count [B,N,15]         accessible points of the atom (0: no atom; -1: an atom of a residue outside `query`);
+ *   sasa_atom [B,N,15]     4 pi (radius + probe_radius)^2 count / n_points (0 where count <= 0);
+ *   sasa_residue [B,N]     sum of sasa_atom over the slots, in slot order;
+ *   sasa_total [B]         sum of sasa_atom over the structure, accumulated in fp64.
+ * Three launches, no atomics, no host synchronisation; memory is O(B N).  Results are bit-identical from run to run and do not
+ * depend on the other samples.  N > PF_SASA_MAX_N or B > 65535 -> PF_E_TOOLARGE. */
+#define PF_SASA_MAX_N 512
+#define PF_SASA_MAX_POINTS 1024
+#define PF_SASA_SLOTS 15
+typedef struct {
+    const float* pos;                   /* [B,N,n_atoms,3] */
+    const unsigned char* atom_mask;     /* [B,N,n_atoms] */
+    const int64_t* aa;                  /* [B,N] */
+    const unsigned char* query;         /* [B,N] optional */
+    const unsigned char* group;         /* [B,N] optional */
+    const float* radius;                /* [21,15] */
+    const float* points;                /* [n_points,3] */
+    float* work;                        /* [B,N,4] scratch */
+    int* count; float* sasa_atom;       /* [B,N,15] */
+    float* sasa_residue;                /* [B,N] */
+    float* sasa_total;                  /* [B] */
+    int* count_own; float* sasa_atom_own; float* sasa_residue_own; float* sasa_total_own;       /* optional, all or none */
+    int B, N, n_atoms, n_points;
+    float probe_radius;                 /* >= 0; 1.4 for water */
+} pf_sasa_args;
+int pf_sasa_fwd(const pf_sasa_args* a, pf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,13 @@ class ViolationsArgs(C.Structure):
                 ("violation_tolerance_factor", C.c_float), ("clash_overlap_tolerance", C.c_float)]
 
 
+class SasaArgs(C.Structure):
+    _fields_ = [("pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("query", _fp), ("group", _fp), ("radius", _fp), ("points", _fp),
+                ("work", _fp), ("count", _fp), ("sasa_atom", _fp), ("sasa_residue", _fp), ("sasa_total", _fp), ("count_own", _fp),
+                ("sasa_atom_own", _fp), ("sasa_residue_own", _fp), ("sasa_total_own", _fp), ("B", _i), ("N", _i), ("n_atoms", _i),
+                ("n_points", _i), ("probe_radius", C.c_float)]
+
+
 class EtBwdArgs(C.Structure):
     _fields_ = [("g_y", _fp), ("h1", _fp), ("h2", _fp), ("wfT_f16", _fp), ("w2T_f16", _fp), ("w1T_f16", _fp),
                 ("g_h2", _fp), ("g_h1", _fp), ("g_x", _fp), ("npairs", C.c_longlong), ("m1", _fp), ("m2", _fp)]
@@ -285,6 +292,7 @@ _SIGNATURES = {
     "pf_tm_align_fwd": ([C.POINTER(TmAlignArgs), _fp], _i),
     "pf_tm_align_lds_bytes": ([_i], _i),
     "pf_violations_fwd": ([C.POINTER(ViolationsArgs), _fp], _i),
+    "pf_sasa_fwd": ([C.POINTER(SasaArgs), _fp], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -3,12 +3,14 @@ reference's sampling drivers), Kabsch RMSD and the pairwise RMSD / sequence-iden
 pf_superpose_fwd (one wave per pair of a work list, fp64 sums and 3x3 SVD); TM-score with a fixed residue correspondence and its
 pairwise matrix on pf_tm_score_fwd (one lane per seed of the TMscore program's search); DSSP secondary structure on pf_dssp_fwd
 (one workgroup per chain slot); AlphaFold's between-residue structural violations (clashes, peptide-bond geometry, CA-CA breaks) on
-pf_violations_fwd (tiled all-pairs pass over the heavy atoms, nothing pair-sized in memory).
+pf_violations_fwd (tiled all-pairs pass over the heavy atoms, nothing pair-sized in memory); Shrake-Rupley solvent-accessible surface
+area, of the whole structure and of every group on its own, on pf_sasa_fwd (a wave per atom, its test points in registers).
 
 Deviation from the reference: `batch_align` selects each sample's masked atoms on their own.  The reference's
 `masked_select(...).reshape(B, -1, 3)` mixes atoms across samples when the per-sample mask counts differ; where the counts are equal
 the results are the same."""
 import ctypes as C
+import math
 
 import torch
 
@@ -432,4 +434,91 @@ def structural_violations(pos, atom_mask, aa, residue_index, query=None, group=N
     for k in ("clash_atom", "clash_atom_cross", "connection_violation", "ca_ca_break"):
         if k in out:
             out[k] = out[k].bool()
+    return out
+
+
+SASA_SLOTS = 15
+SASA_MAX_POINTS, SASA_MAX_N = 1024, 512
+_SASA_RADIUS, _SASA_POINTS = {}, {}
+
+
+def sasa_radius_table():
+    """-> [21,15] float32 CPU tensor: slots 0..13 are `vdw_radius_table`, slot 14 (OXT) is an oxygen in every row."""
+    tab = torch.zeros(21, SASA_SLOTS)
+    tab[:, :VIOLATION_SLOTS] = vdw_radius_table()
+    tab[:, 14] = VDW_RADIUS["O"]
+    return tab
+
+
+def sphere_points(n_points):
+    """-> [P,3] float32 CPU tensor: P points of a golden spiral on the unit sphere, computed in float64 and rounded:
+    y = (2k + 1) / P - 1, r = sqrt(1 - y^2), phi = k pi (3 - sqrt 5), u_k = (r cos phi, y, r sin phi) for k = 0 .. P - 1."""
+    if not isinstance(n_points, int) or isinstance(n_points, bool) or not 1 <= n_points <= SASA_MAX_POINTS:
+        raise ValueError(f"n_points must be an integer in 1..{SASA_MAX_POINTS}, got {n_points!r}")
+    k = torch.arange(n_points, dtype=torch.float64)
+    y = (2.0 * k + 1.0) / n_points - 1.0
+    r = torch.sqrt(1.0 - y * y)
+    phi = k * (math.pi * (3.0 - math.sqrt(5.0)))
+    return torch.stack([r * torch.cos(phi), y, r * torch.sin(phi)], 1).to(torch.float32)
+
+
+def sasa(pos, atom_mask, aa, query=None, group=None, probe_radius=1.4, n_points=960):
+    """pf_sasa_fwd: Shrake-Rupley solvent-accessible surface area of heavy-atom structures (conventions: csrc/sasa.hip).  Bondi
+    radii (`sasa_radius_table`), a probe of 1.4 A and 960 points are also mdtraj's shrake_rupley defaults; there are no hydrogens.
+
+    pos [B,N,A,3] heavy atoms in the package's order, A >= 14, slots 0 .. min(A,15)-1 are read (pos_heavyatom passes as it is);
+    atom_mask [B,N,A]; aa [B,N] residue types in the package's numbering; N <= 512.  query [B,N] (optional): only atoms of query
+    residues are evaluated, every existing atom is still a partner; the others get count -1 and area 0.  group [B,N] bool
+    (optional): adds the *_own outputs, the same quantities with only atoms of residues of the own group as partners -- every group
+    on its own, so sasa_*_own - sasa_* is the area buried by the other group.
+    -> dict of device tensors: count [B,N,15] int32 accessible points, sasa_atom [B,N,15] float32 = 4 pi (radius + probe)^2 count /
+    n_points, sasa_residue [B,N], sasa_total [B]; with `group` count_own, sasa_atom_own, sasa_residue_own, sasa_total_own."""
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 4 or pos.shape[3] != 3 or pos.shape[2] < VIOLATION_SLOTS:
+        raise ValueError(f"pos must be [B,N,A,3] with A >= {VIOLATION_SLOTS}, got {tuple(getattr(pos, 'shape', ()))}")
+    B, N, A, _ = pos.shape
+    if tuple(atom_mask.shape) != (B, N, A):
+        raise ValueError(f"atom_mask must be [B,N,A] = {(B, N, A)}, got {tuple(atom_mask.shape)}")
+    for nm, t in (("aa", aa), ("query", query), ("group", group)):
+        if t is not None and tuple(t.shape) != (B, N):
+            raise ValueError(f"{nm} must be [B,N] = {(B, N)}, got {tuple(t.shape)}")
+    if N > SASA_MAX_N:
+        raise ValueError(f"at most {SASA_MAX_N} residues per structure, got {N}")
+    points = sphere_points(n_points)                # checks n_points
+    probe_radius = float(probe_radius)
+    if not 0.0 <= probe_radius < 1e6:
+        raise ValueError(f"probe_radius must be >= 0, got {probe_radius}")
+    dev = pos.device
+    key = str(dev)
+    keep = [pos.to(dev, torch.float32).contiguous(), atom_mask.to(dev).to(torch.uint8).contiguous(),
+            aa.to(dev, torch.int64).contiguous()]
+    a = _capi.SasaArgs()
+    a.pos, a.atom_mask = _capi.dptr(keep[0], torch.float32, "pos"), _capi.dptr(keep[1], torch.uint8, "atom_mask")
+    a.aa = _capi.dptr(keep[2], torch.int64, "aa")
+    if key not in _SASA_RADIUS:
+        _SASA_RADIUS[key] = sasa_radius_table().contiguous().to(dev)
+    if (key, n_points) not in _SASA_POINTS:
+        _SASA_POINTS[key, n_points] = points.contiguous().to(dev)
+    a.radius, a.points = _SASA_RADIUS[key].data_ptr(), _SASA_POINTS[key, n_points].data_ptr()
+    if query is not None:
+        keep.append(_u8(query, (B, N), dev))
+        a.query = keep[-1].data_ptr()
+    if group is not None:
+        keep.append(_u8(group, (B, N), dev))
+        a.group = keep[-1].data_ptr()
+    S = SASA_SLOTS
+    f32 = lambda *shape: torch.empty(*shape, device=dev)  # noqa: E731
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = {"count": i32(B, N, S), "sasa_atom": f32(B, N, S), "sasa_residue": f32(B, N), "sasa_total": f32(B)}
+    if group is not None:
+        out.update(count_own=i32(B, N, S), sasa_atom_own=f32(B, N, S), sasa_residue_own=f32(B, N), sasa_total_own=f32(B))
+    for k, v in out.items():
+        setattr(a, k, v.data_ptr())
+    a.B, a.N, a.n_atoms, a.n_points, a.probe_radius = B, N, A, n_points, probe_radius
+    if B and N:
+        keep.append(f32(B, N, 4))                   # the residue-sized workspace: centre and padded extent
+        a.work = keep[-1].data_ptr()
+        _capi.check(_capi.load().pf_sasa_fwd(C.byref(a), _capi.stream_ptr()), "pf_sasa_fwd")
+    else:
+        for v in out.values():
+            v.zero_()
     return out

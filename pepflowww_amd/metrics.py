@@ -4,10 +4,10 @@ CA RMSD after superposition, `get_rmsd` 47-59; binding-site ratio, `get_bind_sit
 samples of one complex), without Biopython / tmtools / mdtraj and without writing PDB files; TM-score against the native, novelty
 and TM-score diversity (`structure_scores`); DSSP secondary structure and the secondary-structure ratio, `get_second_stru` / `get_ss`
 79-91 (`secondary_structure`); clashes and broken peptide bonds, AlphaFold's between-residue structural violations
-(`structural_violations`).
+(`structural_violations`); solvent-accessible surface and the area buried between peptide and receptor (`interface_area`).
 
 Every per-residue, per-point and per-atom-pair operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd /
-pf_violations_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
+pf_violations_fwd / pf_sasa_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
@@ -274,4 +274,85 @@ def structural_violations(final, batch, backbone="full_atom", scope="generated")
                "residue_bond_violation": bond, "residue_ca_ca_break": brk, "residue_clash": clash, "atom_clash": v["clash_atom"],
                "atom_clash_receptor": v["clash_atom_cross"], "atom_clash_loss": v["clash_atom_loss"]}
         out.update({k + tag: t for k, t in res.items()})
+    return out
+
+
+_APOLAR = {}
+
+
+def apolar_table():
+    """-> [21,15] bool CPU tensor: heavy-atom slot s of residue type t is a carbon or a sulfur (the first letter of the slot's atom
+    name; row 20, any type outside 0..19: CA and C)."""
+    from .preprocess import _tables
+    names = _tables()["atom_names"]
+    tab = torch.zeros(21, geometry.SASA_SLOTS, dtype=torch.bool)
+    for t in range(20):
+        for s in range(geometry.SASA_SLOTS):
+            tab[t, s] = bool(names[t][s]) and names[t][s][0] in "CS"
+    tab[20, 1] = tab[20, 2] = True
+    return tab
+
+
+def interface_area(final, batch, backbone="full_atom", probe_radius=1.4, n_points=960, min_buried=1.0):
+    """Solvent-accessible surface of each sample's peptide, free and bound, and the area buried between peptide and receptor
+    (geometry.sasa: Shrake-Rupley over the heavy atoms, Bondi radii), for the sample's complex and for its native.  final / batch and
+    the two complexes are those of `structural_violations`: backbone "full_atom" -- generated residues rebuilt with all heavy atoms,
+    the context kept; "frames" -- generated residues as N, CA, C, O only; the native is pos_heavyatom / mask_heavyatom / seqs_1.
+    group = generate_mask & res_mask: the peptide on its own and the receptor on its own against the complex, in one kernel pass.
+
+    -> dict of device tensors.  Per sample [B], float64, in A^2:
+      sasa_peptide_free    surface of the generated residues without the receptor;  sasa_peptide_bound  in the complex;
+      buried_peptide       free - bound;  buried_receptor  the same for the context residues;  bsa  the sum of the two;
+      buried_fraction      buried_peptide / sasa_peptide_free (NaN for a sample without generated residues);
+      buried_apolar_fraction  the share of bsa on carbon and sulfur atoms (NaN where bsa is 0);
+      n_interface_peptide, n_interface_receptor  residues that bury more than min_buried A^2;
+      interface_recovery   |S_sample & S_native| / (|S_native| + 1e-10) over the receptor's interface residues.
+    Per residue [B,L]: residue_buried (float64), interface_residue (bool).  Every key also with `_native` appended (the native's
+    interface_recovery is that of the native against itself).  Relative accessibility is not computed."""
+    if backbone not in ("full_atom", "frames"):
+        raise ValueError(f"backbone must be 'full_atom' or 'frames', got {backbone!r}")
+    geometry.sphere_points(n_points)                # checks n_points
+    if not float(probe_radius) >= 0.0 or not float(min_buried) >= 0.0:
+        raise ValueError(f"probe_radius and min_buried must be >= 0, got {probe_radius}, {min_buried}")
+    dev = _device(batch["generate_mask"], final["trans"], batch["pos_heavyatom"])
+    res_mask = batch["res_mask"].to(dev).bool()
+    gen = batch["generate_mask"].to(dev).bool() & res_mask
+    rec = res_mask & ~gen
+    rotmats, trans, seqs = (final[k].to(dev) for k in ("rotmats", "trans", "seqs"))
+    pos_n, mask_n = batch["pos_heavyatom"].to(dev), batch["mask_heavyatom"].to(dev).bool()
+    if backbone == "full_atom":
+        pos_s, mask_s = full_atom.reconstruct_sample(rotmats, trans, final["angles"].to(dev), seqs, gen, pos_n)
+        mask_s = torch.where(gen[:, :, None], mask_s, mask_n[:, :, :15])
+    else:
+        pos_s, mask_s = full_atom.reconstruct_sample_bb(rotmats, trans, seqs, batch["chain_nb"].to(dev), batch["res_nb"].to(dev),
+                                                        res_mask, gen, pos_n, mask_n)
+    seqs_1 = final["seqs_1"].to(dev)
+    aa_s = torch.where(gen, seqs, seqs_1)
+    key = str(dev)
+    if key not in _APOLAR:
+        _APOLAR[key] = apolar_table().to(dev)
+    has = gen.any(1)
+    nan = torch.full((gen.shape[0],), float("nan"), dtype=torch.float64, device=dev)
+    out, site = {}, {}
+    for tag, pos, mask, aa in (("", pos_s, mask_s, aa_s), ("_native", pos_n, mask_n, seqs_1)):
+        v = geometry.sasa(pos, mask & res_mask[:, :, None], aa, group=gen, probe_radius=probe_radius, n_points=n_points)
+        S = v["sasa_atom"].shape[2]
+        buried_atom = v["sasa_atom_own"].double() - v["sasa_atom"].double()
+        buried = buried_atom.sum(-1)
+        apolar = _APOLAR[key][torch.where((aa < 0) | (aa > 19), 20, aa)][:, :, :S]
+        over = lambda x, m: (x * m).sum(1)  # noqa: E731
+        free, bound = over(v["sasa_atom_own"].double().sum(-1), gen), over(v["sasa_atom"].double().sum(-1), gen)
+        b_pep, b_rec = over(buried, gen), over(buried, rec)
+        bsa = b_pep + b_rec
+        face = buried > float(min_buried)
+        site[tag] = face & rec
+        res = {"sasa_peptide_free": free, "sasa_peptide_bound": bound, "buried_peptide": b_pep, "buried_receptor": b_rec, "bsa": bsa,
+               "buried_fraction": torch.where(has, b_pep / free, nan),
+               "buried_apolar_fraction": (buried_atom * apolar).sum((1, 2)) / bsa,
+               "n_interface_peptide": (face & gen).sum(1), "n_interface_receptor": site[tag].sum(1),
+               "residue_buried": buried, "interface_residue": face}
+        out.update({k + tag: t for k, t in res.items()})
+    n_native = site["_native"].sum(1).double()
+    out["interface_recovery"] = (site[""] & site["_native"]).sum(1).double() / (n_native + 1e-10)
+    out["interface_recovery_native"] = n_native / (n_native + 1e-10)
     return out

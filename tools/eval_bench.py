@@ -11,9 +11,12 @@ pairwise at 64 samples x 25 CA (2 016 pairs), the same peptides inside 128-slot 
 of tests/tmalign_oracle.py on a subset (its CPU time per pair is reported).  Structural violations (pf_violations_fwd, `--only
 violations` runs this leg alone): the heavy atoms of 64 complexes of 144 and of 512 residues, every pair and with query = the 12
 generated residues, against a dense torch restatement of the clash pass ([B,L,L,14,14] tensors) on the device at 8 x 144, and
-metrics.structural_violations at 64 x 144.  Per case: `call` = device events around REPS back-to-back calls of the Python function
+metrics.structural_violations at 64 x 144.  Solvent-accessible surface (pf_sasa_fwd, `--only sasa`): the same complexes of 144 and of
+512 residues at 960 and at 92 points, with and without `group`, metrics.interface_area at 64 x 144, a chunked torch restatement
+([atoms, points, partners] tensors, 8 atoms at a time) on the device at 8 x 144, and the CPU time of the float64 oracle of
+tests/sasa_oracle.py on one complex.  Per case: `call` = device events around REPS back-to-back calls of the Python function
 (host overhead included), `graph` = the same calls captured once as a graph and replayed (device time per call; HIP only).  Prints one JSON
-line.  Usage: python tools/eval_bench.py [--reps 200] [--only violations]"""
+line.  Usage: python tools/eval_bench.py [--reps 200] [--only violations|sasa]"""
 import argparse
 import json
 import os
@@ -28,6 +31,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 from pepflowww_amd import _capi, geometry, metrics, synth  # noqa: E402
 import dssp_build  # noqa: E402
 import dssp_oracle  # noqa: E402
+import sasa_oracle  # noqa: E402
 import tm_oracle  # noqa: E402
 import tmalign_oracle  # noqa: E402
 
@@ -200,16 +204,73 @@ def violation_cases(reps):
     return out
 
 
+def torch_chunked_sasa(pos, exists, R, u, chunk=8):
+    """Shrake-Rupley with torch ops on the device: per sample the existing atoms, `chunk` atoms at a time against all of them
+    ([chunk, P, atoms, 3] tensors) -> accessible points [B,N,15] int32"""
+    B, N, S = exists.shape
+    P = u.shape[0]
+    count = torch.zeros(B, N, S, dtype=torch.int32, device=pos.device)
+    for b in range(B):
+        x, r = pos[b, :, :S][exists[b]], R[b][exists[b]]
+        ids = torch.arange(x.shape[0], device=pos.device)
+        acc = []
+        for c0 in range(0, x.shape[0], chunk):
+            xa, ra = x[c0:c0 + chunk], r[c0:c0 + chunk]
+            t = (xa[:, None, :] - x[None])[:, None] + (ra[:, None, None] * u[None])[:, :, None]
+            hit = ((t * t).sum(-1) < (r * r)[None, None, :]) & (ids[None, None, :] != ids[c0:c0 + chunk, None, None])
+            acc.append(P - hit.any(-1).sum(-1))
+        if acc:
+            count[b][exists[b]] = torch.cat(acc).to(torch.int32)
+    return count
+
+
+def sasa_cases(reps):
+    out = {}
+    table = geometry.sasa_radius_table().cuda()
+    for L in (144, 512):
+        batch = {k: v.cuda() for k, v in synth.make_pocket_batch(64, L, 12, seed=600 + L).items()}
+        pos, mask, aa = batch["pos_heavyatom"], batch["mask_heavyatom"].to(torch.uint8), batch["aa"]
+        gen = batch["generate_mask"].to(torch.uint8)
+        v = geometry.sasa(pos, mask, aa, group=gen)
+        exists = mask.bool() & (table[aa.clamp(0, 20)] > 0)
+        case = {"atoms": int(exists.sum()), "accessible_share": round(float(v["count"].sum()) / (960.0 * int(exists.sum())), 4),
+                "mean_total_A2": round(float(v["sasa_total"].mean()), 1),
+                "mean_buried_A2": round(float((v["sasa_total_own"] - v["sasa_total"]).mean()), 1)}
+        for P in (960, 92):
+            case[f"p{P}"] = timed(lambda: geometry.sasa(pos, mask, aa, n_points=P), reps)
+            case[f"p{P}_group"] = timed(lambda: geometry.sasa(pos, mask, aa, group=gen, n_points=P), reps)
+        case["p960_query_generated"] = timed(lambda: geometry.sasa(pos, mask, aa, query=gen, group=gen), reps)
+        if L == 144:
+            u = geometry.sphere_points(960).cuda()
+            R = table[aa[:8].clamp(0, 20)] + 1.4
+            dense = lambda: torch_chunked_sasa(pos[:8], exists[:8], R, u)  # noqa: E731
+            diff = (dense() - v["count"][:8]).abs()
+            case["chunked_torch_8x144"] = {"atoms_with_another_count": int((diff > 0).sum()), "max_abs_diff_count": int(diff.max()),
+                                           "hip_8x144": timed(lambda: geometry.sasa(pos[:8], mask[:8], aa[:8]), reps),
+                                           "torch": timed(dense, 3, graph=False)}
+            t0 = time.perf_counter()
+            o = sasa_oracle.sasa(pos[0].cpu().numpy(), mask[0].cpu().numpy(), aa[0].cpu().numpy(), table.cpu().numpy(), u.cpu().numpy())
+            case["oracle_cpu_s_per_complex"] = round(time.perf_counter() - t0, 2)
+            d0 = np.abs(o["count"] - v["count"][0].cpu().numpy())
+            case["oracle_atoms_with_another_count"] = int((d0 > o["marginal"]).sum())
+            rot = torch.linalg.qr(torch.randn(64, L, 3, 3, generator=torch.Generator().manual_seed(605)))[0].cuda()
+            final = {"rotmats": rot, "trans": pos[:, :, 1].contiguous(), "angles": batch["torsion_angle"], "seqs": aa, "seqs_1": aa}
+            for bb in ("full_atom", "frames"):
+                case[f"interface_area_{bb}"] = timed(lambda: metrics.interface_area(final, batch, backbone=bb), max(reps // 4, 3), graph=False)
+        out[f"sasa_64x{L}"] = case
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
-    ap.add_argument("--only", choices=["violations"], default=None, help="run one leg alone")
+    ap.add_argument("--only", choices=["violations", "sasa"], default=None, help="run one leg alone")
     args = ap.parse_args()
     _capi.load()
     dev = torch.device("cuda")
     out = {"device": torch.cuda.get_device_name(0)}
-    if args.only == "violations":
-        out.update(violation_cases(args.reps))
+    if args.only in ("violations", "sasa"):
+        out.update(violation_cases(args.reps) if args.only == "violations" else sasa_cases(args.reps))
         print(json.dumps(out))
         return
     for name, G in (("pairwise_64x25", 1), ("pairwise_16x64x25", 16)):
@@ -270,6 +331,7 @@ def main():
         out[f"secondary_structure_64x25_{bb}"] = {"hip": timed(lambda: metrics.secondary_structure(final, batch, backbone=bb),
                                                                args.reps, graph=False)}
     out.update(violation_cases(args.reps))
+    out.update(sasa_cases(args.reps))
     print(json.dumps(out))
 
 
