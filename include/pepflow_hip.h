@@ -996,6 +996,60 @@ typedef struct {
 } pf_sasa_args;
 int pf_sasa_fwd(const pf_sasa_args* a, pf_stream_t stream);
 
+/* ---- torsion angles and side-chain packing (ABI 64, added entry points) -------------------------------------------------------
+ * pf_torsions_fwd: omega, phi, psi, psi_o (N, CA, C, O) and chi1-chi4 of B structures of N residues; the conventions are listed in
+ * csrc/torsions.hip.  pos [B,N,n_atoms,3] in the package's heavy-atom order, n_atoms >= 14, slots 0..13 are read; atom_mask
+ * [B,N,n_atoms]; aa [B,N]; residue_index [B,N] optional (absent: consecutive positions are bonded); chi_atoms [21,4,4] the heavy-atom
+ * slots of chi1-4 by type, -1 where the type has no such angle.
+ *   angles [B,N,8]     radians in [0, 2 pi): omega, phi, psi, psi_o, chi1..chi4; 0 where not defined (never NaN);
+ *   defined [B,N,8]    1 where the four atoms are in atom_mask, the neighbour a backbone angle needs is bonded (residue_index grows by
+ *                      exactly 1), the type has the chi, and no part perpendicular to the central bond has zero length.
+ * psi_o is slot 0 of the reference's get_torsion_angle; on rebuilt coordinates it is the model's first angle + pi.  fp32, atan2 form,
+ * from coordinate differences.  One launch, no scratch, no host synchronisation.  angles must be 8-byte and defined 4-byte aligned.
+ * B > 65535 -> PF_E_TOOLARGE.
+ *
+ * pf_sidechain_compare_fwd: for every pair (i, j) of pairs [P,2], x[i] against y[j] residue by residue: wrapped angle errors per slot,
+ * residues with every chi within correct_tol, and the deviation of side-chain atoms 4..13 in the residues' own backbone frames.
+ * angles_* / defined_* are pf_torsions_fwd's outputs (16- and 8-byte aligned); periodic [21,4]: chi k of the type is pi-periodic;
+ * swap [21,4]: two pairs (a1, b1, a2, b2) of equivalent slots of the type, (0, 0) unused.  y may alias x.
+ *   err_sum [P,8] (fp64, radians), err_count, within [P,8]   over the residues where both angles are defined (slots 3..7: and the
+ *                      types are equal and in 0..19); within counts error <= correct_tol;
+ *   res_with_chi, res_correct [P]   residues with a compared chi; those with every compared chi within correct_tol;
+ *   sc_sq_sum [P] (fp64), sc_atoms [P], sc_rmsd [P] (NaN when sc_atoms is 0)   squared frame-local deviations, the smaller of the
+ *                      plain and the slot-exchanged sum per residue;
+ *   err [P,N,8] (NaN: not compared), sc_sq [P,N], sc_n [P,N], swapped [P,N]   optional, all four or none.
+ * A pair with an index out of range gives zero counts and NaN.  One launch, a workgroup per pair looping over N, fixed-order sums, no
+ * floating-point atomics: bit-identical from run to run and independent of the rest of the list.  N * 8 > INT_MAX -> PF_E_TOOLARGE. */
+typedef struct {
+    const float* pos;                   /* [B,N,n_atoms,3] */
+    const unsigned char* atom_mask;     /* [B,N,n_atoms] */
+    const int64_t* aa;                  /* [B,N] */
+    const int* residue_index;           /* [B,N] optional */
+    const int* chi_atoms;               /* [21,4,4] */
+    float* angles;                      /* [B,N,8] */
+    unsigned char* defined;             /* [B,N,8] */
+    int B, N, n_atoms;
+} pf_torsions_args;
+int pf_torsions_fwd(const pf_torsions_args* a, pf_stream_t stream);
+
+typedef struct {
+    const float* pos_x; const float* pos_y;                         /* [Bx,N,n_atoms_x,3], [By,N,n_atoms_y,3] */
+    const unsigned char* mask_x; const unsigned char* mask_y;       /* [Bx,N,n_atoms_x], [By,N,n_atoms_y] */
+    const int64_t* aa_x; const int64_t* aa_y;                       /* [Bx,N], [By,N] */
+    const float* angles_x; const float* angles_y;                   /* [Bx,N,8], [By,N,8] */
+    const unsigned char* defined_x; const unsigned char* defined_y; /* [Bx,N,8], [By,N,8] */
+    const int* pairs;                                               /* [P,2] */
+    const unsigned char* periodic;                                  /* [21,4] */
+    const unsigned char* swap;                                      /* [21,4] */
+    double* err_sum; int* err_count; int* within;                   /* [P,8] */
+    int* res_with_chi; int* res_correct;                            /* [P] */
+    double* sc_sq_sum; int* sc_atoms; float* sc_rmsd;               /* [P] */
+    float* err; float* sc_sq; int* sc_n; unsigned char* swapped;    /* [P,N,8], [P,N] x 3: optional, all or none */
+    int Bx, By, N, P, n_atoms_x, n_atoms_y;
+    float correct_tol;                                              /* radians, >= 0 */
+} pf_sidechain_compare_args;
+int pf_sidechain_compare_fwd(const pf_sidechain_compare_args* a, pf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -211,6 +211,19 @@ class SasaArgs(C.Structure):
                 ("n_points", _i), ("probe_radius", C.c_float)]
 
 
+class TorsionsArgs(C.Structure):
+    _fields_ = [("pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("residue_index", _fp), ("chi_atoms", _fp), ("angles", _fp),
+                ("defined", _fp), ("B", _i), ("N", _i), ("n_atoms", _i)]
+
+
+class SidechainCompareArgs(C.Structure):
+    _fields_ = [("pos_x", _fp), ("pos_y", _fp), ("mask_x", _fp), ("mask_y", _fp), ("aa_x", _fp), ("aa_y", _fp), ("angles_x", _fp),
+                ("angles_y", _fp), ("defined_x", _fp), ("defined_y", _fp), ("pairs", _fp), ("periodic", _fp), ("swap", _fp),
+                ("err_sum", _fp), ("err_count", _fp), ("within", _fp), ("res_with_chi", _fp), ("res_correct", _fp), ("sc_sq_sum", _fp),
+                ("sc_atoms", _fp), ("sc_rmsd", _fp), ("err", _fp), ("sc_sq", _fp), ("sc_n", _fp), ("swapped", _fp),
+                ("Bx", _i), ("By", _i), ("N", _i), ("P", _i), ("n_atoms_x", _i), ("n_atoms_y", _i), ("correct_tol", C.c_float)]
+
+
 class EtBwdArgs(C.Structure):
     _fields_ = [("g_y", _fp), ("h1", _fp), ("h2", _fp), ("wfT_f16", _fp), ("w2T_f16", _fp), ("w1T_f16", _fp),
                 ("g_h2", _fp), ("g_h1", _fp), ("g_x", _fp), ("npairs", C.c_longlong), ("m1", _fp), ("m2", _fp)]
@@ -293,6 +306,8 @@ _SIGNATURES = {
     "pf_tm_align_lds_bytes": ([_i], _i),
     "pf_violations_fwd": ([C.POINTER(ViolationsArgs), _fp], _i),
     "pf_sasa_fwd": ([C.POINTER(SasaArgs), _fp], _i),
+    "pf_torsions_fwd": ([C.POINTER(TorsionsArgs), _fp], _i),
+    "pf_sidechain_compare_fwd": ([C.POINTER(SidechainCompareArgs), _fp], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

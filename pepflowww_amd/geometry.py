@@ -4,7 +4,11 @@ pf_superpose_fwd (one wave per pair of a work list, fp64 sums and 3x3 SVD); TM-s
 pairwise matrix on pf_tm_score_fwd (one lane per seed of the TMscore program's search); DSSP secondary structure on pf_dssp_fwd
 (one workgroup per chain slot); AlphaFold's between-residue structural violations (clashes, peptide-bond geometry, CA-CA breaks) on
 pf_violations_fwd (tiled all-pairs pass over the heavy atoms, nothing pair-sized in memory); Shrake-Rupley solvent-accessible surface
-area, of the whole structure and of every group on its own, on pf_sasa_fwd (a wave per atom, its test points in registers).
+area, of the whole structure and of every group on its own, on pf_sasa_fwd (a wave per atom, its test points in registers); torsion
+angles (omega, phi, psi, the N-CA-C-O angle and chi1-chi4) on pf_torsions_fwd (tiles of residues staged in LDS with a one-residue halo)
+and the side-chain packing comparison of pairs of structures -- wrapped chi errors, residues with every chi within a tolerance, the
+deviation of side-chain atoms in the backbone frame with equivalent atoms exchanged -- on pf_sidechain_compare_fwd (a workgroup per
+pair, fixed-order sums).
 
 Deviation from the reference: `batch_align` selects each sample's masked atoms on their own.  The reference's
 `masked_select(...).reshape(B, -1, 3)` mixes atoms across samples when the per-sample mask counts differ; where the counts are equal
@@ -521,4 +525,164 @@ def sasa(pos, atom_mask, aa, query=None, group=None, probe_radius=1.4, n_points=
     else:
         for v in out.values():
             v.zero_()
+    return out
+
+
+TORSION_NAMES = ("omega", "phi", "psi", "psi_o", "chi1", "chi2", "chi3", "chi4")
+# Stated from chemistry, resolved against the package's own atom-name table: the chi angles whose two end atoms are equivalent (the
+# angle is defined up to pi), and the atom pairs that a 180 degree flip of that chi exchanges.
+PI_PERIODIC_CHI = {"ASP": 2, "GLU": 3, "PHE": 2, "TYR": 2}
+EQUIVALENT_ATOMS = {"ASP": (("OD1", "OD2"),), "GLU": (("OE1", "OE2"),), "PHE": (("CD1", "CD2"), ("CE1", "CE2")),
+                    "TYR": (("CD1", "CD2"), ("CE1", "CE2"))}
+_TORSION_TABLES = {}
+
+
+def chi_atom_table():
+    """-> [21,4,4] int32 CPU tensor: the heavy-atom slots of chi1-4 of each residue type (data/chi_atoms.npz), -1: no such angle"""
+    from .preprocess import _tables
+    return _tables()["chi_atom_idx"][:21].to(torch.int32).contiguous()
+
+
+def pi_periodic_table():
+    """-> [21,4] bool CPU tensor: chi k + 1 of type t is pi-periodic (PI_PERIODIC_CHI by residue name)"""
+    from .preprocess import _tables
+    tab = torch.zeros(21, 4, dtype=torch.bool)
+    for name, chi in PI_PERIODIC_CHI.items():
+        tab[_tables()["res_index"][name], chi - 1] = True
+    return tab
+
+
+def swap_table():
+    """-> [21,4] uint8 CPU tensor: (a1, b1, a2, b2), the slots of up to two pairs of equivalent atoms of type t (EQUIVALENT_ATOMS by
+    residue and atom name); (0, 0) where unused"""
+    from .preprocess import _tables
+    t = _tables()
+    tab = torch.zeros(21, 4, dtype=torch.uint8)
+    for name, pairs in EQUIVALENT_ATOMS.items():
+        r = t["res_index"][name]
+        for k, (u, v) in enumerate(pairs):
+            tab[r, 2 * k], tab[r, 2 * k + 1] = t["atom_names"][r].index(u), t["atom_names"][r].index(v)
+    return tab
+
+
+def _bytes(t, dev):
+    """a mask as uint8 on the device; a bool tensor is reinterpreted, not copied"""
+    t = t.to(dev)
+    return (t.view(torch.uint8) if t.dtype == torch.bool else t.to(torch.uint8)).contiguous()
+
+
+def _torsion_tables(dev):
+    key = str(dev)
+    if key not in _TORSION_TABLES:
+        _TORSION_TABLES[key] = (chi_atom_table().to(dev), pi_periodic_table().to(torch.uint8).to(dev), swap_table().to(dev))
+    return _TORSION_TABLES[key]
+
+
+def torsion_angles(pos, atom_mask, aa, residue_index=None):
+    """pf_torsions_fwd: the torsion angles of heavy-atom structures (conventions: csrc/torsions.hip).
+
+    pos [B,N,A,3] heavy atoms in the package's order, A >= 14, slots 0..13 are read (pos_heavyatom passes as it is); atom_mask
+    [B,N,A]; aa [B,N] residue types in the package's numbering; residue_index [B,N] (optional, metrics.residue_index): residues are
+    bonded where it grows by exactly 1; None: consecutive positions are bonded.
+    -> dict of device tensors: angles [B,N,8] float32 in [0, 2 pi), slots TORSION_NAMES: omega (CA(n-1), C(n-1), N, CA), phi, psi,
+    psi_o (N, CA, C, O: slot 0 of preprocess.get_torsion_angle; on coordinates rebuilt by full_atom it is the model's first angle
+    + pi), chi1..chi4; defined [B,N,8] bool: all four atoms in atom_mask, the neighbour bonded (backbone angles), the type has the chi,
+    no degenerate geometry.  Undefined angles are 0, never NaN."""
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 4 or pos.shape[3] != 3 or pos.shape[2] < VIOLATION_SLOTS:
+        raise ValueError(f"pos must be [B,N,A,3] with A >= {VIOLATION_SLOTS}, got {tuple(getattr(pos, 'shape', ()))}")
+    B, N, A, _ = pos.shape
+    if tuple(atom_mask.shape) != (B, N, A):
+        raise ValueError(f"atom_mask must be [B,N,A] = {(B, N, A)}, got {tuple(atom_mask.shape)}")
+    for nm, t in (("aa", aa), ("residue_index", residue_index)):
+        if t is not None and tuple(t.shape) != (B, N):
+            raise ValueError(f"{nm} must be [B,N] = {(B, N)}, got {tuple(t.shape)}")
+    dev = pos.device
+    keep = [pos.to(dev, torch.float32).contiguous(), _bytes(atom_mask, dev), aa.to(dev, torch.int64).contiguous()]
+    a = _capi.TorsionsArgs()
+    a.pos, a.atom_mask = _capi.dptr(keep[0], torch.float32, "pos"), _capi.dptr(keep[1], torch.uint8, "atom_mask")
+    a.aa = _capi.dptr(keep[2], torch.int64, "aa")
+    if residue_index is not None:
+        keep.append(residue_index.to(dev, torch.int32).contiguous())
+        a.residue_index = keep[-1].data_ptr()
+    a.chi_atoms = _torsion_tables(dev)[0].data_ptr()
+    angles = torch.empty(B, N, 8, device=dev)
+    defined = torch.empty(B, N, 8, dtype=torch.uint8, device=dev)
+    a.angles, a.defined = angles.data_ptr(), defined.data_ptr()
+    a.B, a.N, a.n_atoms = B, N, A
+    if B and N:
+        _capi.check(_capi.load().pf_torsions_fwd(C.byref(a), _capi.stream_ptr()), "pf_torsions_fwd")
+    return {"angles": angles, "defined": defined.view(torch.bool)}
+
+
+_COMPARE_KEYS = ("pos", "atom_mask", "aa", "angles", "defined")
+
+
+def sidechain_compare(x, y, pairs, correct_tol=math.radians(20), per_residue=False):
+    """pf_sidechain_compare_fwd over the work list `pairs` [P,2] (pair p = (i, j): x[i] against y[j], residue by residue).
+
+    x, y: dicts with pos [B.,N,A.,3], atom_mask [B.,N,A.], aa [B.,N] and the angles / defined [B.,N,8] of `torsion_angles` (y may be
+    x).  correct_tol: radians.
+    -> dict of device tensors.  Per pair and angle slot [P,8]: err_sum float64 (radians), err_count, within int32 -- over the residues
+    where both angles are defined (slots 3..7: and the types are equal and in 0..19), the absolute difference wrapped to [0, pi], to
+    [0, pi/2] for the pi-periodic chi (PI_PERIODIC_CHI); within counts errors <= correct_tol.  Per pair [P]: res_with_chi (residues
+    with a compared chi), res_correct (those with every compared chi within correct_tol), sc_sq_sum float64, sc_atoms int32, sc_rmsd
+    float32 (NaN without atoms): side-chain slots 4..13 of residues of equal type, each in its own backbone frame, the smaller of the
+    sum as it is and with EQUIVALENT_ATOMS exchanged.  With `per_residue`: err [P,N,8] (NaN where not compared), sc_sq [P,N], sc_n
+    [P,N] int32, swapped [P,N] bool."""
+    for nm, d in (("x", x), ("y", y)):
+        if not isinstance(d, dict) or any(k not in d for k in _COMPARE_KEYS):
+            raise ValueError(f"{nm} must be a dict with {_COMPARE_KEYS}")
+        pos = d["pos"]
+        if not isinstance(pos, torch.Tensor) or pos.dim() != 4 or pos.shape[3] != 3 or pos.shape[2] < VIOLATION_SLOTS:
+            raise ValueError(f"{nm}['pos'] must be [B,N,A,3] with A >= {VIOLATION_SLOTS}, got {tuple(getattr(pos, 'shape', ()))}")
+        B, N, A, _ = pos.shape
+        for k, shape in (("atom_mask", (B, N, A)), ("aa", (B, N)), ("angles", (B, N, 8)), ("defined", (B, N, 8))):
+            if tuple(d[k].shape) != shape:
+                raise ValueError(f"{nm}[{k!r}] must be {shape}, got {tuple(d[k].shape)}")
+    Bx, N, Ax, _ = x["pos"].shape
+    By, Ny, Ay, _ = y["pos"].shape
+    if Ny != N:
+        raise ValueError(f"x and y must have the same number of residues, got {N} and {Ny}")
+    if N == 0 or Bx == 0 or By == 0:
+        raise ValueError("sidechain_compare needs at least one structure of at least one residue on each side")
+    pairs = torch.as_tensor(pairs)
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"pairs must be [P,2], got {tuple(pairs.shape)}")
+    correct_tol = float(correct_tol)
+    if not 0.0 <= correct_tol <= math.pi:
+        raise ValueError(f"correct_tol must be in [0, pi] radians, got {correct_tol}")
+    dev = x["pos"].device
+
+    def aligned(t, n):      # the kernel reads angles as float4 and defined 8 bytes at a time: a view at an odd offset is copied
+        return t if t.data_ptr() % n == 0 else t.clone()
+
+    def side(d):
+        return [d["pos"].to(dev, torch.float32).contiguous(), _bytes(d["atom_mask"], dev), d["aa"].to(dev, torch.int64).contiguous(),
+                aligned(d["angles"].to(dev, torch.float32).contiguous(), 16), aligned(_bytes(d["defined"], dev), 8)]
+    kx = side(x)
+    ky = kx if y is x else side(y)
+    pairs = pairs.to(dev, torch.int32).contiguous()
+    P = pairs.shape[0]
+    a = _capi.SidechainCompareArgs()
+    for tag, kk in (("x", kx), ("y", ky)):
+        for name, t, dt in zip(("pos", "mask", "aa", "angles", "defined"), kk,
+                               (torch.float32, torch.uint8, torch.int64, torch.float32, torch.uint8)):
+            setattr(a, f"{name}_{tag}", _capi.dptr(t, dt, f"{tag}.{name}"))
+    a.pairs = _capi.dptr(pairs, torch.int32, "pairs")
+    tabs = _torsion_tables(dev)
+    a.periodic, a.swap = tabs[1].data_ptr(), tabs[2].data_ptr()
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = {"err_sum": torch.empty(P, 8, dtype=torch.float64, device=dev), "err_count": i32(P, 8), "within": i32(P, 8),
+           "res_with_chi": i32(P), "res_correct": i32(P), "sc_sq_sum": torch.empty(P, dtype=torch.float64, device=dev),
+           "sc_atoms": i32(P), "sc_rmsd": torch.empty(P, device=dev)}
+    if per_residue:
+        out.update(err=torch.empty(P, N, 8, device=dev), sc_sq=torch.empty(P, N, device=dev), sc_n=i32(P, N),
+                   swapped=torch.empty(P, N, dtype=torch.uint8, device=dev))
+    for k, v in out.items():
+        setattr(a, k, v.data_ptr())
+    a.Bx, a.By, a.N, a.P, a.n_atoms_x, a.n_atoms_y, a.correct_tol = Bx, By, N, P, Ax, Ay, correct_tol
+    if P:
+        _capi.check(_capi.load().pf_sidechain_compare_fwd(C.byref(a), _capi.stream_ptr()), "pf_sidechain_compare_fwd")
+    if per_residue:
+        out["swapped"] = out["swapped"].view(torch.bool)
     return out

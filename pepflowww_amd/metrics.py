@@ -4,10 +4,12 @@ CA RMSD after superposition, `get_rmsd` 47-59; binding-site ratio, `get_bind_sit
 samples of one complex), without Biopython / tmtools / mdtraj and without writing PDB files; TM-score against the native, novelty
 and TM-score diversity (`structure_scores`); DSSP secondary structure and the secondary-structure ratio, `get_second_stru` / `get_ss`
 79-91 (`secondary_structure`); clashes and broken peptide bonds, AlphaFold's between-residue structural violations
-(`structural_violations`); solvent-accessible surface and the area buried between peptide and receptor (`interface_area`).
+(`structural_violations`); solvent-accessible surface and the area buried between peptide and receptor (`interface_area`); the
+side-chain packing table, chi1-chi4 errors against the native and the share of residues with every chi within a tolerance
+(`sidechain_packing`).
 
 Every per-residue, per-point and per-atom-pair operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd /
-pf_violations_fwd / pf_sasa_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
+pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
@@ -356,3 +358,68 @@ def interface_area(final, batch, backbone="full_atom", probe_radius=1.4, n_point
     out["interface_recovery"] = (site[""] & site["_native"]).sum(1).double() / (n_native + 1e-10)
     out["interface_recovery_native"] = n_native / (n_native + 1e-10)
     return out
+
+
+CIS_OMEGA_DEG = 30.0        # an omega within 30 degrees of 0 is a cis peptide bond
+
+
+def sidechain_packing(final, batch, correct_tol_deg=20.0):
+    """Side-chain packing of each sample against its native: the chi1-chi4 errors and the share of residues whose chi angles are all
+    within correct_tol_deg (geometry.torsion_angles on both structures, geometry.sidechain_compare on the diagonal).  final / batch as
+    in `structural_violations`: the sample is reconstruct_sample(rotmats, trans, angles, seqs) with types where(generate, seqs,
+    seqs_1), the native pos_heavyatom / mask_heavyatom / seqs_1; bonded neighbours come from `residue_index`.  Only generated residues
+    count.  A chi is compared where both structures define it and the residue types are equal, so the table is that of a
+    `sample(..., sample_bb=False, sample_seq=False)` run; with sampled sequences it covers the recovered positions.  The pi-periodic
+    chi (geometry.PI_PERIODIC_CHI) are compared modulo pi.
+
+    -> dict of device tensors.  Per sample, in degrees, NaN where nothing is compared: chi_mae [B,4], chi_correct [B,4] (the share
+    within the tolerance), residue_correct [B] (residues with every compared chi within it, over residues with a compared chi),
+    psi_o_mae, phi_mae, psi_mae [B] (psi_o: the N-CA-C-O angle, which is the model's first angle + pi), sc_rmsd [B] (side-chain atoms
+    in the backbone frame, equivalent atoms exchanged where that is closer, in A), n_chi [B,4] int32, cis_fraction [B] (the sample's
+    defined omegas of generated residues within 30 degrees of 0).  Pooled over the compared residues of the batch, float64:
+    chi_mae_pooled [4], chi_correct_pooled [4], residue_correct_pooled.  By the native's residue type: chi_mae_by_type [20,4]
+    (float64), n_chi_by_type [20,4].  Per residue: chi_err [B,L,4] (degrees, NaN where not compared), residue_sc_rmsd [B,L] (NaN
+    where no atom is compared), swapped [B,L] bool, angles_sample, angles_native [B,L,8] (radians, geometry.TORSION_NAMES; before
+    the restriction to generated residues)."""
+    tol = float(correct_tol_deg)
+    if not 0.0 <= tol <= 180.0:
+        raise ValueError(f"correct_tol_deg must be in [0, 180], got {correct_tol_deg}")
+    dev = _device(batch["generate_mask"], final["trans"], batch["pos_heavyatom"])
+    res_mask = batch["res_mask"].to(dev).bool()
+    gen = batch["generate_mask"].to(dev).bool() & res_mask
+    rotmats, trans, seqs = (final[k].to(dev) for k in ("rotmats", "trans", "seqs"))
+    seqs_1 = final["seqs_1"].to(dev)
+    pos_n, mask_n = batch["pos_heavyatom"].to(dev), batch["mask_heavyatom"].to(dev).bool()
+    pos_s, mask_s = full_atom.reconstruct_sample(rotmats, trans, final["angles"].to(dev), seqs, gen, pos_n)
+    mask_s = torch.where(gen[:, :, None], mask_s, mask_n[:, :, :15])
+    aa_s = torch.where(gen, seqs, seqs_1)
+    index = residue_index(batch["chain_nb"].to(dev), batch["res_nb"].to(dev), res_mask)
+    B, L = gen.shape
+    sides = []
+    for pos, mask, aa in ((pos_s, mask_s, aa_s), (pos_n, mask_n, seqs_1)):
+        t = geometry.torsion_angles(pos, mask & res_mask[:, :, None], aa, index)
+        sides.append(dict(pos=pos, atom_mask=mask & gen[:, :, None], aa=aa, angles=t["angles"], defined=t["defined"] & gen[:, :, None]))
+    ids = torch.arange(B, dtype=torch.int32, device=dev)
+    c = geometry.sidechain_compare(sides[0], sides[1], torch.stack([ids, ids], 1), correct_tol=math.radians(tol), per_residue=True)
+
+    deg = 180.0 / math.pi
+    cnt = c["err_count"].double()
+    mae = c["err_sum"] * deg / cnt                          # 0 / 0: NaN where nothing is compared
+    share = c["within"].double() / cnt
+    omega, om_def = sides[0]["angles"][:, :, 0], sides[0]["defined"][:, :, 0]
+    cis = om_def & ((omega <= math.radians(CIS_OMEGA_DEG)) | (omega >= math.radians(360.0 - CIS_OMEGA_DEG)))
+    chi_err = c["err"][:, :, 4:] * deg
+    compared = ~torch.isnan(chi_err)
+    types = seqs_1.clamp(0, 19).reshape(-1)
+    by_sum = torch.zeros(20, 4, dtype=torch.float64, device=dev).index_add_(0, types, torch.nan_to_num(chi_err).double().reshape(-1, 4))
+    by_n = torch.zeros(20, 4, dtype=torch.int64, device=dev).index_add_(0, types, compared.reshape(-1, 4).long())
+    sc_n = c["sc_n"].double()
+    return {"chi_mae": mae[:, 4:], "chi_correct": share[:, 4:], "residue_correct": c["res_correct"].double() / c["res_with_chi"].double(),
+            "psi_o_mae": mae[:, 3], "phi_mae": mae[:, 1], "psi_mae": mae[:, 2], "sc_rmsd": c["sc_rmsd"], "n_chi": c["err_count"][:, 4:],
+            "cis_fraction": cis.sum(1).double() / om_def.sum(1).double(),
+            "chi_mae_pooled": c["err_sum"][:, 4:].sum(0) * deg / cnt[:, 4:].sum(0),
+            "chi_correct_pooled": c["within"][:, 4:].sum(0).double() / cnt[:, 4:].sum(0),
+            "residue_correct_pooled": c["res_correct"].sum().double() / c["res_with_chi"].sum().double(),
+            "chi_mae_by_type": by_sum / by_n.double(), "n_chi_by_type": by_n,
+            "chi_err": chi_err, "residue_sc_rmsd": torch.sqrt(c["sc_sq"].double() / sc_n).float(), "swapped": c["swapped"],
+            "angles_sample": sides[0]["angles"], "angles_native": sides[1]["angles"]}

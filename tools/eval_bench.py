@@ -14,9 +14,12 @@ generated residues, against a dense torch restatement of the clash pass ([B,L,L,
 metrics.structural_violations at 64 x 144.  Solvent-accessible surface (pf_sasa_fwd, `--only sasa`): the same complexes of 144 and of
 512 residues at 960 and at 92 points, with and without `group`, metrics.interface_area at 64 x 144, a chunked torch restatement
 ([atoms, points, partners] tensors, 8 atoms at a time) on the device at 8 x 144, and the CPU time of the float64 oracle of
-tests/sasa_oracle.py on one complex.  Per case: `call` = device events around REPS back-to-back calls of the Python function
+tests/sasa_oracle.py on one complex.  Torsion angles and side-chain packing (pf_torsions_fwd, pf_sidechain_compare_fwd, `--only
+torsions`): 64 complexes of 144 residues, torsion_angles of both structures and sidechain_compare on the diagonal, against
+preprocess.get_torsion_angle (the torch-op form: N-CA-C-O and chi1-4 of one structure, no comparison) looped over the 64 structures
+on the device, and metrics.sidechain_packing.  Per case: `call` = device events around REPS back-to-back calls of the Python function
 (host overhead included), `graph` = the same calls captured once as a graph and replayed (device time per call; HIP only).  Prints one JSON
-line.  Usage: python tools/eval_bench.py [--reps 200] [--only violations|sasa]"""
+line.  Usage: python tools/eval_bench.py [--reps 200] [--only violations|sasa|torsions]"""
 import argparse
 import json
 import os
@@ -261,16 +264,49 @@ def sasa_cases(reps):
     return out
 
 
+def torsion_cases(reps):
+    from pepflowww_amd.preprocess import get_torsion_angle
+    B, L = 64, 144
+    batch = {k: v.cuda() for k, v in synth.make_pocket_batch(B, L, 12, seed=744).items()}
+    pos, mask, aa = batch["pos_heavyatom"], batch["mask_heavyatom"].to(torch.uint8), batch["aa"]
+    index = metrics.residue_index(batch["chain_nb"], batch["res_nb"], batch["res_mask"])
+    pos2 = (pos + 0.3 * torch.randn(pos.shape, generator=torch.Generator().manual_seed(745)).cuda()).contiguous()
+    ids = torch.arange(B, dtype=torch.int32, device="cuda")
+    diag = torch.stack([ids, ids], 1)
+
+    def side(p):
+        t = geometry.torsion_angles(p, mask, aa, index)
+        return dict(pos=p, atom_mask=mask, aa=aa, angles=t["angles"], defined=t["defined"])
+
+    x, y = side(pos2), side(pos)
+    both = lambda: geometry.sidechain_compare(side(pos2), side(pos), diag)  # noqa: E731
+    c = both()
+    case = {"angles_defined": int(y["defined"].sum()), "chi_compared": int(c["err_count"][:, 4:].sum()),
+            "angles_one_structure": timed(lambda: geometry.torsion_angles(pos, mask, aa, index), reps),
+            "compare_diagonal": timed(lambda: geometry.sidechain_compare(x, y, diag), reps),
+            "compare_diagonal_per_residue": timed(lambda: geometry.sidechain_compare(x, y, diag, per_residue=True), reps),
+            "angles_x2_and_compare": timed(both, reps),
+            "torch_get_torsion_angle_x64": timed(lambda: [get_torsion_angle(pos[b], aa[b]) for b in range(B)], max(reps // 20, 3), graph=False)}
+    ref = torch.stack([get_torsion_angle(pos[b], aa[b])[0] for b in range(B)])
+    d = (y["angles"][:, :, 3:] - ref).abs()
+    d = torch.minimum(d, 2 * np.pi - d)[y["defined"][:, :, 3:]]
+    case["median_abs_diff_to_torch_rad"] = float(d.median())
+    rot = torch.linalg.qr(torch.randn(B, L, 3, 3, generator=torch.Generator().manual_seed(746)))[0].cuda()
+    final = {"rotmats": rot, "trans": pos[:, :, 1].contiguous(), "angles": batch["torsion_angle"], "seqs": aa, "seqs_1": aa}
+    case["sidechain_packing"] = timed(lambda: metrics.sidechain_packing(final, batch), max(reps // 4, 3), graph=False)
+    return {"torsions_64x144": case}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
-    ap.add_argument("--only", choices=["violations", "sasa"], default=None, help="run one leg alone")
+    ap.add_argument("--only", choices=["violations", "sasa", "torsions"], default=None, help="run one leg alone")
     args = ap.parse_args()
     _capi.load()
     dev = torch.device("cuda")
     out = {"device": torch.cuda.get_device_name(0)}
-    if args.only in ("violations", "sasa"):
-        out.update(violation_cases(args.reps) if args.only == "violations" else sasa_cases(args.reps))
+    if args.only in ("violations", "sasa", "torsions"):
+        out.update({"violations": violation_cases, "sasa": sasa_cases, "torsions": torsion_cases}[args.only](args.reps))
         print(json.dumps(out))
         return
     for name, G in (("pairwise_64x25", 1), ("pairwise_16x64x25", 16)):
@@ -332,6 +368,7 @@ def main():
                                                                args.reps, graph=False)}
     out.update(violation_cases(args.reps))
     out.update(sasa_cases(args.reps))
+    out.update(torsion_cases(args.reps))
     print(json.dumps(out))
 
 
