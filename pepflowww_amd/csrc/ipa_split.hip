@@ -1542,56 +1542,67 @@ __global__ __launch_bounds__(64 * ZW) void ipa_pair_kernel(pf_ipa_attn_args a) {
 // bytes per pair instead of the 256 of z):  o_pair[h][c] = b_dz[c] + sum_j P[h][j] dz[i][j][c].  One wave per query row, four rows
 // per workgroup, no workgroup barrier; the contraction over keys is a [heads padded to 16] x [4 keys] x [16 channels] fp32 MFMA.
 //   B operand of lane (r = channel, g): dz[i][key][r] with key = 16 u + 4 t + g in MFMA (u, t): the 64 lanes of one load
-//   instruction read 256 CONTIGUOUS bytes (dword each);  A operand: P[h = r][16 u + 4 t + g], staged in LDS in the order
-//   [h][u][g][t] so that a lane reads its four t as one float4.
+//   instruction read 256 CONTIGUOUS bytes (dword each);  A operand: P[h = r & 7][16 u + 4 t + g], staged in LDS in the order
+//   [h][u][g][t] (g rotated per key group, pdz_slot) so that a lane reads its four t as one float4.
 // (A VALU form -- float4 loads, lane = 4 channels of a key, 32 partial sums per lane reduced over 16 lanes -- measured 28 us at
 //  B=64, L=128, of which ~290 of ~700 instructions per row were the cross-lane reduction.)
-template <int NG, bool D16 = false>            // 16-key groups: 16 NG >= L; D16: dz is f16
-__global__ __launch_bounds__(256) void ipa_pair_dz_kernel(pf_ipa_attn_args a) {
-    constexpr int LPZ = 16 * NG;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+// The staged P image of a row: [h][u][g'][t] floats with g' = (g + (u >> 1)) & 3 and a head stride of 16 NG + 8.  The rotation of
+// the g slot with the key group puts the 32 lanes of one staging ds_write_b32 (8 key groups x 4 t) on 32 different banks, and the 8
+// floats between the heads put the 16 lanes of a ds_read_b128 group (8 heads x 2 g) on the 16 different 16-byte slots of a bank row
+// (unpadded and unrotated the stores were 4-way and the reads 8-way conflicted: profiles/r07/README.md).
+__device__ __forceinline__ int pdz_slot(int u, int g) { return 16 * u + 4 * ((g + (u >> 1)) & 3); }
+
+template <class T> __device__ __forceinline__ T ld_boff(const void* base, unsigned byte_off) { return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off); }
+
+// One row over its first NU key groups, straight-line (no branch between the loads: a per-group `if` made hipcc drain vmcnt group
+// by group).  Keys from Le on read row Le - 1 (a real key, finite) against P = 0: acc + 0 x finite = acc bit for bit.
+template <int NG, int NU, bool D16, bool V4>   // V4: L % 4 == 0, P rows are read as float4
+__device__ __forceinline__ void pair_dz_row(const pf_ipa_attn_args& a, float* PL, long row, long b, long i, int Le, int lane) {
+    constexpr int LPU = 16 * NU, LDP = 16 * NG + 8, NP = (2 * LPU + 63) / 64;
     const int r = lane & 15, g = lane >> 4;
     const int L = a.L;
-    const long row = (long)blockIdx.x * 4 + wave;                // b * L + i
-    if (row >= (long)a.B * L) return;
-    const long b = row / L, i = row - b * L;
-    const int Le = a.key_end ? min(__builtin_amdgcn_readfirstlane(a.key_end[b]), L) : L;
-    if (i >= Le) return;                                         // (wave-uniform; nothing below synchronises the workgroup)
-    const int nge = (Le + 15) >> 4;
-    float* PL = smem + wave * 8 * LPZ;                           // [8][LPZ] probabilities of this row (0 from Le on), permuted
-    const float* drow = a.dz + (size_t)row * L * 16 + r;
-    const _Float16* drow16 = reinterpret_cast<const _Float16*>(a.dz) + (size_t)row * L * 16 + r;
-    float bv[NG][4];
-    _Float16 bv16[NG][4];
+    // P first: vmcnt retires in order, so the staging below waits for these loads only, not for the 8 KiB of dz behind them
+    float4 pv[NP];
+    const float* prow = a.p_out + ((size_t)b * H * L + i) * L;
+    if constexpr (V4) {
 #pragma unroll
-    for (int u = 0; u < NG; ++u)
-        if (u < nge) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const size_t off = (size_t)min(16 * u + 4 * t + g, L - 1) * 16;
-                if constexpr (D16) bv16[u][t] = drow16[off];
-                else bv[u][t] = drow[off];
-            }
+        for (int k = 0; k < NP; ++k) {                           // float4 pieces of the 8 head rows: keys j .. j + 3 = slots g = 0 .. 3
+            const int idx = lane + 64 * k, hh = min(idx / (LPU / 4), H - 1), j = 4 * (idx % (LPU / 4));
+            pv[k] = ld_boff<float4>(prow, 4u * (unsigned)(hh * L * L + (j < Le ? j : 0)));   // (unconditional: no branch around the load)
         }
+    }
+    const float* drow = a.dz + (size_t)row * L * 16;             // (wave-uniform bases + 32-bit lane BYTE offsets: one address register per load)
+    const _Float16* drow16 = reinterpret_cast<const _Float16*>(a.dz) + (size_t)row * L * 16;
+    float bv[NU][4];
+    _Float16 bv16[NU][4];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const unsigned off = (unsigned)min(16 * u + 4 * t + g, Le - 1) * 16u + r;
+            if constexpr (D16) bv16[u][t] = ld_boff<_Float16>(drow16, 2u * off);
+            else bv[u][t] = ld_boff<float>(drow, 4u * off);
+        }
+    }
     const float bdz = a.b_dz[r];
-    if ((L & 3) == 0) {
-        for (int idx = lane; idx < LPZ * 2; idx += 64) {         // float4 pieces of the 8 head rows: keys j .. j + 3 = slots g = 0 .. 3
-            const int hh = idx / (LPZ / 4), j = 4 * (idx - hh * (LPZ / 4));
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (j < Le) {
-                v = *reinterpret_cast<const float4*>(a.p_out + ((b * H + hh) * L + i) * L + j);
-                if (j + 1 >= Le) v.y = 0.f;                      // (the score kernel does not write beyond key Le - 1)
-                if (j + 2 >= Le) v.z = 0.f;
-                if (j + 3 >= Le) v.w = 0.f;
+    if constexpr (V4) {
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            const int idx = lane + 64 * k, hh = idx / (LPU / 4), j = 4 * (idx % (LPU / 4));
+            if (2 * LPU % 64 == 0 || idx < 2 * LPU) {
+                const float4 v = pv[k];                          // (the score kernel does not write beyond key Le - 1)
+                float* d = PL + hh * LDP + ((j >> 2) & 3);
+                const int u = j >> 4;
+                d[pdz_slot(u, 0)] = j < Le ? v.x : 0.f;
+                d[pdz_slot(u, 1)] = j + 1 < Le ? v.y : 0.f;
+                d[pdz_slot(u, 2)] = j + 2 < Le ? v.z : 0.f;
+                d[pdz_slot(u, 3)] = j + 3 < Le ? v.w : 0.f;
             }
-            float* d = PL + hh * LPZ + (j & ~15) + ((j >> 2) & 3);
-            d[0] = v.x; d[4] = v.y; d[8] = v.z; d[12] = v.w;
         }
     } else {
-        for (int idx = lane; idx < LPZ * 8; idx += 64) {
-            const int hh = idx / LPZ, j = idx - hh * LPZ;
-            PL[hh * LPZ + (j & ~15) + 4 * (j & 3) + ((j >> 2) & 3)] = j < Le ? a.p_out[((b * H + hh) * L + i) * L + j] : 0.f;
+        for (int idx = lane; idx < LPU * 8; idx += 64) {
+            const int hh = idx / LPU, j = idx - hh * LPU;
+            PL[hh * LDP + pdz_slot(j >> 4, j & 3) + ((j >> 2) & 3)] = j < Le ? ld_boff<float>(prow, 4u * (unsigned)(hh * L * L + j)) : 0.f;
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // wave-private LDS hand-off
@@ -1599,28 +1610,52 @@ __global__ __launch_bounds__(256) void ipa_pair_dz_kernel(pf_ipa_attn_args a) {
     f32x4 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const float* pl = PL + (r & 7) * LPZ + 4 * g;
-    const float keep = r < 8 ? 1.f : 0.f;                        // MFMA rows 8..15 are padding
+    // A rows 8..15 (lanes r >= 8) repeat heads 0..7: they only reach D rows 8..15, which are not stored
+    const float* pl = PL + (r & 7) * LDP;
 #pragma unroll
-    for (int u = 0; u < NG; ++u) {
-        if (u < nge) {
-            const float4 pa = *reinterpret_cast<const float4*>(pl + 16 * u);   // (keys from Le on: P = 0 times a clamped, finite row)
-            if constexpr (D16) {
+    for (int u = 0; u < NU; ++u) {
+        const float4 pa = *reinterpret_cast<const float4*>(pl + pdz_slot(u, g));
+        if constexpr (D16) {
 #pragma unroll
-                for (int t = 0; t < 4; ++t) bv[u][t] = (float)bv16[u][t];
-            }
-            acc[0] = mfma16(pa.x * keep, bv[u][0], acc[0]);
-            acc[1] = mfma16(pa.y * keep, bv[u][1], acc[1]);
-            acc[2] = mfma16(pa.z * keep, bv[u][2], acc[2]);
-            acc[3] = mfma16(pa.w * keep, bv[u][3], acc[3]);
+            for (int t = 0; t < 4; ++t) bv[u][t] = (float)bv16[u][t];
         }
+        acc[0] = mfma16(pa.x, bv[u][0], acc[0]);
+        acc[1] = mfma16(pa.y, bv[u][1], acc[1]);
+        acc[2] = mfma16(pa.z, bv[u][2], acc[2]);
+        acc[3] = mfma16(pa.w, bv[u][3], acc[3]);
     }
     // D: lane (r = channel, g), register e -> head 4 g + e
     if (g < 2) {
-        float* f = a.feats + (size_t)row * PF_IPA_FEATS + 1408 + r;
+        float* f = a.feats + (size_t)row * PF_IPA_FEATS + 1408;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) f[(4 * g + e) * 16] = ((acc[0][e] + acc[1][e]) + (acc[2][e] + acc[3][e])) + bdz;
+        for (int e = 0; e < 4; ++e) f[(unsigned)((4 * g + e) * 16 + r)] = ((acc[0][e] + acc[1][e]) + (acc[2][e] + acc[3][e])) + bdz;
     }
+}
+
+// a short sample (key_end) takes the instantiation with NU = its key groups, rounded up to NG - 2 k
+template <int NG, int NU, bool D16, bool V4>
+__device__ __forceinline__ void pair_dz_pick(const pf_ipa_attn_args& a, float* PL, long row, long b, long i, int Le, int nge, int lane) {
+    if constexpr (NU <= 2) pair_dz_row<NG, NU, D16, V4>(a, PL, row, b, i, Le, lane);
+    else {
+        if (nge > NU - 2) pair_dz_row<NG, NU, D16, V4>(a, PL, row, b, i, Le, lane);
+        else pair_dz_pick<NG, NU - 2, D16, V4>(a, PL, row, b, i, Le, nge, lane);
+    }
+}
+
+template <int NG, bool D16 = false>            // 16-key groups: 16 NG >= L; D16: dz is f16
+__global__ __launch_bounds__(256, NG <= 8 ? 8 : NG <= 11 ? 5 : 4) void ipa_pair_dz_kernel(pf_ipa_attn_args a) {   // NG <= 8: 8 waves per SIMD (<= 64 registers): B=64, L=128 is ONE round of waves; beyond: what the kernel had
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int L = a.L;
+    const long row = (long)blockIdx.x * 4 + wave;                // b * L + i
+    if (row >= (long)a.B * L) return;
+    const long b = (unsigned)row / (unsigned)L, i = row - b * L; // (rows < 2^31: pf_ipa_split_launch)
+    const int Le = a.key_end ? min(__builtin_amdgcn_readfirstlane(a.key_end[b]), L) : L;
+    if (i >= Le) return;                                         // (wave-uniform; nothing below synchronises the workgroup)
+    float* PL = smem + wave * 8 * (16 * NG + 8);                 // [8][16 NG + 8] probabilities of this row (0 from Le on), permuted
+    // (the two forms apart: joined in one body, hipcc drained the P loads with vmcnt(0) before it issued the first dz load)
+    if ((L & 3) == 0) pair_dz_pick<NG, NG, D16, true>(a, PL, row, b, i, Le, (Le + 15) >> 4, lane);
+    else pair_dz_pick<NG, NG, D16, false>(a, PL, row, b, i, Le, (Le + 15) >> 4, lane);
 }
 
 // The same for f16 pair values (f16 mode): 2-byte loads are as many load instructions as 4-byte ones and the MFMA form above
@@ -1874,7 +1909,7 @@ int pf_ipa_split_launch(const pf_ipa_attn_args* a, hipStream_t s) {
     if (ng > 16 || rows > 0x7fffffffL) return PF_E_TOOLARGE;
     if (a->dz) {
         const dim3 gridd((unsigned)((rows + 3) / 4));
-        const size_t ldsd = (size_t)4 * 8 * 16 * ng * sizeof(float);
+        const size_t ldsd = (size_t)4 * 8 * (a->dz_f16 ? 16 * ng : 16 * ng + 8) * sizeof(float);   // (fp32: head rows padded, pdz_slot)
         switch (ng) {
 #define PF_PAIRDZ_CASE(N) case N: if (a->dz_f16) hipLaunchKernelGGL(ipa_pair_dz16_kernel<N>, gridd, dim3(256), ldsd, s, *a); else hipLaunchKernelGGL((ipa_pair_dz_kernel<N, false>), gridd, dim3(256), ldsd, s, *a); break;
             PF_PAIRDZ_CASE(1) PF_PAIRDZ_CASE(2) PF_PAIRDZ_CASE(3) PF_PAIRDZ_CASE(4) PF_PAIRDZ_CASE(5) PF_PAIRDZ_CASE(6) PF_PAIRDZ_CASE(7)
