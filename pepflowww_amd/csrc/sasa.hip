@@ -42,6 +42,7 @@
 //   total_kernel   one block per sample: the fp64 sums.
 #include "common.h"
 #include "../../include/pepflow_hip.h"
+#include "eval_dev.h"
 
 namespace {
 
@@ -55,8 +56,6 @@ __host__ __device__ inline size_t sasa_lds_bytes(int N, int nw) {
     const size_t cap = (size_t)N * SL;
     return 16 * cap + 16 * (size_t)nw * LCAP + 64 + 2 * ((cap + 1) & ~(size_t)1) + 2 * PF_SASA_MAX_N + (size_t)nw * LCAP;
 }
-
-__device__ __forceinline__ int type_row(int64_t t) { return t < 0 || t > 20 ? 20 : (int)t; }
 
 __global__ __launch_bounds__(256) void bounds_kernel(pf_sasa_args a) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -305,18 +304,6 @@ __global__ __launch_bounds__(NT_MAX) void sasa_kernel(pf_sasa_args a) {
     }
 }
 
-// sum over the block in a fixed order (tree over thread ids); every thread gets the result
-__device__ __forceinline__ double block_sum(double v, double* red, int tid) {
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (tid < h) red[tid] += red[tid + h];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 __global__ __launch_bounds__(256) void total_kernel(pf_sasa_args a) {
     __shared__ double red[256];
     const int tid = threadIdx.x;
@@ -326,8 +313,8 @@ __global__ __launch_bounds__(256) void total_kernel(pf_sasa_args a) {
         s += (double)a.sasa_atom[b * na + i];
         if (a.sasa_atom_own) s_own += (double)a.sasa_atom_own[b * na + i];
     }
-    s = block_sum(s, red, tid);
-    s_own = block_sum(s_own, red, tid);
+    s = block_sum<256>(s, red, tid);
+    s_own = block_sum<256>(s_own, red, tid);
     if (tid == 0) {
         a.sasa_total[b] = (float)s;
         if (a.sasa_total_own) a.sasa_total_own[b] = (float)s_own;

@@ -55,6 +55,7 @@
 #include "common.h"
 #include "../../include/pepflow_hip.h"
 #include "superpose_dev.h"
+#include "eval_dev.h"
 
 namespace {
 
@@ -158,12 +159,6 @@ __device__ __forceinline__ double ta_d2(const Xf& f, const double x[3], const do
 }
 
 __device__ __forceinline__ double ta_term(double d2, double d02) { return 1.0 / (1.0 + d2 / d02); }
-
-__device__ __forceinline__ void ta_load3(const float* p, double v[3]) {
-    v[0] = p[0];
-    v[1] = p[1];
-    v[2] = p[2];
-}
 
 // the canonical rotation of a two-point fit (see the header)
 __device__ __forceinline__ void ta_two_point(const double a[3], const double b[3], double R[3][3]) {
@@ -330,19 +325,6 @@ __device__ __forceinline__ double ta_quick(int n, const Par& P, Get&& get) {
     return s2 > s ? s2 : s;
 }
 
-__device__ __forceinline__ bool ta_better(double s, long long c, double s2, long long c2) {  // first of equal scores (c smaller)
-    return s > s2 || (s == s2 && c < c2);
-}
-
-__device__ __forceinline__ void ta_wave_best(double& s, long long& c) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double s2 = __shfl_xor(s, m);
-        const long long c2 = __shfl_xor(c, m);
-        if (ta_better(s2, c2, s, c)) { s = s2; c = c2; }
-    }
-}
-
 __device__ __forceinline__ void ta_bcast(Xf& f, int src) {
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -378,8 +360,8 @@ __device__ __forceinline__ double ta_search(const Lds& L, int n, int step, doubl
     for (int u = 0; u < nl; ++u) total += ta_start_count(n - ta_seed_len(n, nl, u), step);
     const double d02 = d0 * d0;
     auto get = [&](int k, double xv[3], double yv[3]) {
-        ta_load3(pts + 6 * k, xv);
-        ta_load3(pts + 6 * k + 3, yv);
+        load3d(pts + 6 * k, xv);
+        load3d(pts + 6 * k + 3, yv);
     };
     double best = -1.0;
     long long bestc = LLONG_MAX;
@@ -463,7 +445,7 @@ __device__ __forceinline__ double ta_search(const Lds& L, int n, int step, doubl
     }
     double wb = best;
     long long wc = bestc;
-    ta_wave_best(wb, wc);
+    wave_best(wb, wc);
     const unsigned long long hold = __ballot(wc != LLONG_MAX && bestc == wc);
     const int src = hold ? __ffsll((long long)hold) - 1 : 0;
     ta_bcast(bf, src);
@@ -514,7 +496,7 @@ __device__ __forceinline__ void ta_dp(const Lds& L, int Lx, int Ly, int mode, co
         unsigned char sx = 0;
         if (row_ok) {
             double xv[3];
-            ta_load3(L.xs + 3 * (i - 1), xv);
+            load3d(L.xs + 3 * (i - 1), xv);
             if (mode != 1) ta_apply(f, xv, xx);
             sx = L.ssx[i - 1];
         }
@@ -541,7 +523,7 @@ __device__ __forceinline__ void ta_dp(const Lds& L, int Lx, int Ly, int mode, co
                     s = sx == L.ssy[j - 1] ? 1.0 : 0.0;
                 } else {
                     double yv[3];
-                    ta_load3(L.ys + 3 * (j - 1), yv);
+                    load3d(L.ys + 3 * (j - 1), yv);
                     const double e0 = xx[0] - yv[0], e1 = xx[1] - yv[1], e2 = xx[2] - yv[2];
                     s = ta_term(e0 * e0 + e1 * e1 + e2 * e2, d02);
                     if (mode == 2 && sx == L.ssy[j - 1]) s = s + 0.5;
@@ -601,7 +583,7 @@ __device__ __forceinline__ unsigned char ta_sec(const float* xs, int L, int i) {
     if (i < 2 || i + 2 >= L) return 0;
     double p[5][3];
 #pragma unroll
-    for (int a = 0; a < 5; ++a) ta_load3(xs + 3 * (i - 2 + a), p[a]);
+    for (int a = 0; a < 5; ++a) load3d(xs + 3 * (i - 2 + a), p[a]);
     auto dd = [&](int a, int b) {
         const double e0 = p[a][0] - p[b][0], e1 = p[a][1] - p[b][1], e2 = p[a][2] - p[b][2];
         return sqrt(e0 * e0 + e1 * e1 + e2 * e2);
@@ -626,8 +608,8 @@ __device__ __forceinline__ void ta_max_frag(const float* zs, int L, int& start, 
         int best = 0, bs = 0, be = 0, j = 1, st = 0;
         for (int i = 1; i < L; ++i) {
             double a[3], b[3];
-            ta_load3(zs + 3 * (i - 1), a);
-            ta_load3(zs + 3 * i, b);
+            load3d(zs + 3 * (i - 1), a);
+            load3d(zs + 3 * i, b);
             const double e0 = b[0] - a[0], e1 = b[1] - a[1], e2 = b[2] - a[2];
             if (e0 * e0 + e1 * e1 + e2 * e2 < cut) {
                 ++j;
@@ -680,8 +662,8 @@ __device__ __forceinline__ void ta_thread(const Lds& L, const Par& P, int n1, in
         if (k > n2) continue;
         const Seg s = ta_seg(k, yrun, run0, lrun, Lx, Ly);
         const double sc = ta_quick(s.cnt, P, [&](int u, double xv[3], double yv[3]) {
-            ta_load3(L.xs + 3 * (s.xo + u), xv);
-            ta_load3(L.ys + 3 * (s.yo + u), yv);
+            load3d(L.xs + 3 * (s.xo + u), xv);
+            load3d(L.ys + 3 * (s.yo + u), yv);
         });
         if (sc >= best) { best = sc; bk = k; }
     }
@@ -868,15 +850,15 @@ __global__ __launch_bounds__(64) void tm_align_kernel(pf_tm_align_args a, int Lc
                     Xf g;
                     ta_fit(nf, [](int) { return true; },
                            [&](int k, double xv[3], double yv[3]) {
-                               ta_load3(L.xs + 3 * (i0 + k), xv);
-                               ta_load3(L.ys + 3 * (j0 + k), yv);
+                               load3d(L.xs + 3 * (i0 + k), xv);
+                               load3d(L.ys + 3 * (j0 + k), yv);
                            },
                            g);
                     ta_dp(L, Lx, Ly, 0, g, d01 * d01, 0.0, L.mdp, lane);
                     const int n = ta_compact(L, L.mdp, Ly, lane);
                     const double gl = ta_quick(n, P, [&](int k, double xv[3], double yv[3]) {
-                        ta_load3(L.pts + 6 * k, xv);
-                        ta_load3(L.pts + 6 * k + 3, yv);
+                        load3d(L.pts + 6 * k, xv);
+                        load3d(L.pts + 6 * k + 3, yv);
                     });
                     ta_sync();
                     if (gl > glmax) {
@@ -903,8 +885,8 @@ __global__ __launch_bounds__(64) void tm_align_kernel(pf_tm_align_args a, int Lc
         Xf g;
         ta_fit(n, [](int) { return true; },
                [&](int k, double xv[3], double yv[3]) {
-                   ta_load3(L.pts + 6 * k, xv);
-                   ta_load3(L.pts + 6 * k + 3, yv);
+                   load3d(L.pts + 6 * k, xv);
+                   load3d(L.pts + 6 * k + 3, yv);
                },
                g);
         ta_sync();
@@ -958,8 +940,8 @@ __global__ __launch_bounds__(64) void tm_align_kernel(pf_tm_align_args a, int Lc
         bool keep = false;
         double xv[3], yv[3];
         if (i >= 0) {
-            ta_load3(L.xs + 3 * i, xv);
-            ta_load3(L.ys + 3 * j, yv);
+            load3d(L.xs + 3 * i, xv);
+            load3d(L.ys + 3 * j, yv);
             keep = sqrt(ta_d2(f, xv, yv)) <= P.d8;
         }
         if (j < Ly) L.kept[j] = keep;
@@ -978,8 +960,8 @@ __global__ __launch_bounds__(64) void tm_align_kernel(pf_tm_align_args a, int Lc
     double rmsd = qnan;
     if (n8 > 0) {
         auto getp = [&](int k, double xv[3], double yv[3]) {
-            ta_load3(L.pts + 6 * k, xv);
-            ta_load3(L.pts + 6 * k + 3, yv);
+            load3d(L.pts + 6 * k, xv);
+            load3d(L.pts + 6 * k + 3, yv);
         };
         Xf g;
         ta_fit(n8, [](int) { return true; }, getp, g);
@@ -1041,7 +1023,7 @@ __global__ __launch_bounds__(64) void tm_align_kernel(pf_tm_align_args a, int Lc
     if (a.aligned)
         for (int k = lane; k < N; k += 64) {
             double xv[3], o[3];
-            ta_load3(X + (size_t)k * 3, xv);
+            load3d(X + (size_t)k * 3, xv);
             ta_apply(f, xv, o);
 #pragma unroll
             for (int r = 0; r < 3; ++r) a.aligned[((size_t)p * N + k) * 3 + r] = (float)o[r];

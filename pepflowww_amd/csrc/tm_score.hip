@@ -13,6 +13,7 @@
 #include "common.h"
 #include "../../include/pepflow_hip.h"
 #include "superpose_dev.h"
+#include "eval_dev.h"
 
 namespace {
 
@@ -56,20 +57,6 @@ inline int tm_chunks(int N) {
         most = c > most ? c : most;
     }
     return most > 0 ? (most + 63) / 64 : 1;
-}
-
-__device__ __forceinline__ bool tm_better(double s, long long c, double s2, long long c2) {
-    return s > s2 || (s == s2 && c < c2);
-}
-
-// the wave's best (score, candidate): a maximum under a total order, so the result does not depend on the butterfly's pairing
-__device__ __forceinline__ void tm_wave_best(double& s, long long& c) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double s2 = __shfl_xor(s, m);
-        const long long c2 = __shfl_xor(c, m);
-        if (tm_better(s2, c2, s, c)) { s = s2; c = c2; }
-    }
 }
 
 __device__ __forceinline__ void tm_point(const float* pts, int k, double xv[3], double yv[3]) {
@@ -298,7 +285,7 @@ __global__ __launch_bounds__(256) void tm_search_kernel(pf_tm_score_args a, int 
 
     double wb = best;
     long long wc = bestc;
-    tm_wave_best(wb, wc);
+    wave_best(wb, wc);
     TmSlot* slot = work + (size_t)p * nchunk + chunk;
     if (lane == 0) {
         slot->score = wb;
@@ -332,9 +319,9 @@ __global__ __launch_bounds__(256) void tm_finish_kernel(pf_tm_score_args a, int 
     long long c = LLONG_MAX;
     for (int u = lane; u < nchunk; u += 64) {
         const TmSlot* sl = work + (size_t)p * nchunk + u;
-        if (tm_better(sl->score, sl->cand, s, c)) { s = sl->score; c = sl->cand; }
+        if (cand_better(sl->score, sl->cand, s, c)) { s = sl->score; c = sl->cand; }
     }
-    tm_wave_best(s, c);
+    wave_best(s, c);
     const bool ok = n >= 3 && c != LLONG_MAX;
     double R[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}}, t[3];
     const float qnan = __int_as_float(0x7fc00000);

@@ -37,6 +37,7 @@
 // 1); the only atomics are integer counters in LDS.  One writer per output: bit-identical from run to run and independent of the list.
 #include "common.h"
 #include "../../include/pepflow_hip.h"
+#include "eval_dev.h"
 
 namespace {
 
@@ -59,7 +60,6 @@ __device__ __forceinline__ void stage_rows(const float* pos, const unsigned char
     }
 }
 
-__device__ __forceinline__ int clamp_type(int64_t t) { return (t < 0 || t > 20) ? 20 : (int)t; }
 
 // the dihedral of four staged points; false where it is not defined (the value is then not used)
 __device__ __forceinline__ bool dihedral(const float* p0, const float* p1, const float* p2, const float* p3, float& angle) {
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(NT) void torsions_kernel(pf_torsions_args a) {
         const int n = r0 - 1 + tid;
         const bool in = n >= 0 && n < N;
         sidx[tid] = in ? (a.residue_index ? a.residue_index[b * N + n] : n) : 0;
-        saa[tid] = in ? clamp_type(a.aa[b * N + n]) : 20;
+        saa[tid] = in ? type_row(a.aa[b * N + n]) : 20;
     }
     for (int i = tid; i < 21 * 16; i += NT) schi[i] = a.chi_atoms[i];
     __syncthreads();
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(CT) void sidechain_compare_kernel(pf_sidechain_comp
         for (int k = 0; k < NA; ++k) err[k] = __builtin_nanf("");
         if (valid) {
             const size_t rx = i * N + n, ry = j * N + n;
-            const int tx = clamp_type(a.aa_x[rx]), ty = clamp_type(a.aa_y[ry]);
+            const int tx = type_row(a.aa_x[rx]), ty = type_row(a.aa_y[ry]);
             const bool same = tx == ty && tx < 20;
             const float4 ax0 = reinterpret_cast<const float4*>(a.angles_x + rx * NA)[0], ax1 = reinterpret_cast<const float4*>(a.angles_x + rx * NA)[1];
             const float4 ay0 = reinterpret_cast<const float4*>(a.angles_y + ry * NA)[0], ay1 = reinterpret_cast<const float4*>(a.angles_y + ry * NA)[1];

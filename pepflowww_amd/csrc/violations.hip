@@ -41,6 +41,7 @@
 //   reduce_kernel      one block per sample: the connection pass (a thread per residue) and the per-sample means.
 #include "common.h"
 #include "../../include/pepflow_hip.h"
+#include "eval_dev.h"
 
 namespace {
 
@@ -214,10 +215,6 @@ struct Conn {
     bool viol, ca_break;
 };
 
-__device__ __forceinline__ void ld3d(const float* p, double v[3]) {
-    v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
-}
-
 __device__ __forceinline__ double dist_eps(const double p[3], const double q[3]) {
     const double x = p[0] - q[0], y = p[1] - q[1], z = p[2] - q[2];
     return sqrt(BOND_EPS + ((x * x + y * y) + z * z));
@@ -231,10 +228,10 @@ __device__ __forceinline__ Conn connection(const pf_violations_args& a, size_t b
     const unsigned char* M0 = a.atom_mask + r0 * a.n_atoms;
     const unsigned char* M1 = a.atom_mask + r1 * a.n_atoms;
     double ca[3], c[3], n1[3], ca1[3];
-    ld3d(P0 + 3, ca);
-    ld3d(P0 + 6, c);
-    ld3d(P1, n1);
-    ld3d(P1 + 3, ca1);
+    load3d(P0 + 3, ca);
+    load3d(P0 + 6, c);
+    load3d(P1, n1);
+    load3d(P1 + 3, ca1);
     const bool nogap = (long long)a.residue_index[r1] - (long long)a.residue_index[r0] == 1;
     const bool pro = a.aa[r1] == a.pro;
     const double tf = (double)a.violation_tolerance_factor;
@@ -268,18 +265,6 @@ __device__ __forceinline__ Conn connection(const pf_violations_args& a, size_t b
     o.m_ca = M0[1] && M1[1] && nogap;
     o.ca_break = o.m_ca && dist_eps(ca, ca1) - CA_CA > CA_CA_TOL;
     return o;
-}
-
-// sum over the block in a fixed order (tree over thread ids); every thread gets the result
-__device__ __forceinline__ double block_sum(double v, double* red, int tid) {
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int h = NT / 2; h > 0; h >>= 1) {
-        if (tid < h) red[tid] += red[tid + h];
-        __syncthreads();
-    }
-    return red[0];
 }
 
 __global__ __launch_bounds__(NT) void reduce_kernel(pf_violations_args a) {
@@ -316,11 +301,11 @@ __global__ __launch_bounds__(NT) void reduce_kernel(pf_violations_args a) {
         s_cl += (double)a.clash_atom_loss[b * na + i];
         c_cl += (double)a.clash_atom_pairs[b * na + i];
     }
-    s_cn = block_sum(s_cn, red, tid); c_cn = block_sum(c_cn, red, tid);
-    s_a1 = block_sum(s_a1, red, tid); c_a1 = block_sum(c_a1, red, tid);
-    s_a2 = block_sum(s_a2, red, tid); c_a2 = block_sum(c_a2, red, tid);
-    s_ca = block_sum(s_ca, red, tid); c_ca = block_sum(c_ca, red, tid);
-    s_cl = block_sum(s_cl, red, tid); c_cl = block_sum(c_cl, red, tid);
+    s_cn = block_sum<NT>(s_cn, red, tid); c_cn = block_sum<NT>(c_cn, red, tid);
+    s_a1 = block_sum<NT>(s_a1, red, tid); c_a1 = block_sum<NT>(c_a1, red, tid);
+    s_a2 = block_sum<NT>(s_a2, red, tid); c_a2 = block_sum<NT>(c_a2, red, tid);
+    s_ca = block_sum<NT>(s_ca, red, tid); c_ca = block_sum<NT>(c_ca, red, tid);
+    s_cl = block_sum<NT>(s_cl, red, tid); c_cl = block_sum<NT>(c_cl, red, tid);
     if (tid == 0) {
         a.bond_c_n_loss_mean[b] = (float)(s_cn / (c_cn + BOND_EPS));
         a.angle_ca_c_n_loss_mean[b] = (float)(s_a1 / (c_a1 + BOND_EPS));

@@ -1,14 +1,12 @@
-"""Superposition on the device: drop-in for `align` / `batch_align` of pepflow/modules/common/geometry.py:18-56 (imported by the
-reference's sampling drivers), Kabsch RMSD and the pairwise RMSD / sequence-identity matrix of a set of samples, on the HIP kernel
-pf_superpose_fwd (one wave per pair of a work list, fp64 sums and 3x3 SVD); TM-score with a fixed residue correspondence and its
-pairwise matrix on pf_tm_score_fwd (one lane per seed of the TMscore program's search); DSSP secondary structure on pf_dssp_fwd
-(one workgroup per chain slot); AlphaFold's between-residue structural violations (clashes, peptide-bond geometry, CA-CA breaks) on
-pf_violations_fwd (tiled all-pairs pass over the heavy atoms, nothing pair-sized in memory); Shrake-Rupley solvent-accessible surface
-area, of the whole structure and of every group on its own, on pf_sasa_fwd (a wave per atom, its test points in registers); torsion
-angles (omega, phi, psi, the N-CA-C-O angle and chi1-chi4) on pf_torsions_fwd (tiles of residues staged in LDS with a one-residue halo)
-and the side-chain packing comparison of pairs of structures -- wrapped chi errors, residues with every chi within a tolerance, the
-deviation of side-chain atoms in the backbone frame with equivalent atoms exchanged -- on pf_sidechain_compare_fwd (a workgroup per
-pair, fixed-order sums).
+"""Evaluation geometry on the device: thin wrappers that check their arguments, bind device pointers into one argument struct and
+launch one HIP entry point each (the kernels and their conventions are described in csrc/*.hip).
+
+Two input families, one binding path each:
+  pair work lists   point sets x [Bx,N,3] / y [By,N,3] with masks and `pairs` [P,2] -- `_pair_inputs`: superpose (and align, batch_align,
+                    superpose_rmsd), tm_score, tm_align and their pairwise_* matrices (`_within_groups`, `_mirrored`);
+  heavy-atom structures   pos [B,N,A,3], atom_mask [B,N,A] and per-residue [B,N] tensors -- `_structure`: structural_violations, sasa,
+                    torsion_angles and each side of sidechain_compare (dssp reads the same pos with a residue mask).
+`_bind_in` / `_bind_out` fill the struct, `_as_bool` turns the byte outputs into bool, `_table` keeps the per-device constant tables.
 
 Deviation from the reference: `batch_align` selects each sample's masked atoms on their own.  The reference's
 `masked_select(...).reshape(B, -1, 3)` mixes atoms across samples when the per-sample mask counts differ; where the counts are equal
@@ -20,13 +18,112 @@ import torch
 
 from . import _capi
 
-
-def _f32(t, shape, dev):
-    return t.to(dev, torch.float32).reshape(shape).contiguous()
+_TABLES = {}
 
 
-def _u8(t, shape, dev):
-    return t.to(dev).to(torch.uint8).reshape(shape).contiguous()
+def _table(name, dev, make, *key):
+    """the constant table `name` on `dev`, built by make() (a CPU tensor) on first use; key: what else it depends on (n_points)"""
+    k = (name, str(dev)) + key
+    if k not in _TABLES:
+        _TABLES[k] = make().contiguous().to(dev)
+    return _TABLES[k]
+
+
+def _f32(t, dev):
+    return t.to(dev, torch.float32).contiguous()
+
+
+def _bytes(t, dev):
+    """a mask as uint8 on the device; a bool tensor is reinterpreted, not copied"""
+    t = t.to(dev)
+    return (t.view(torch.uint8) if t.dtype == torch.bool else t.to(torch.uint8)).contiguous()
+
+
+def _bind_in(a, **tensors):
+    """device pointers of the inputs into the argument struct `a` (None: the field stays null); a CPU tensor raises, no fallback"""
+    for k, t in tensors.items():
+        if t is not None:
+            setattr(a, k, _capi.dptr(t, t.dtype, k))
+
+
+def _bind_out(a, out):
+    for k, t in out.items():
+        setattr(a, k, t.data_ptr())
+
+
+def _as_bool(out, *keys):
+    """the byte outputs among `keys` that are there, as bool (the kernels write 0 / 1: a reinterpretation)"""
+    for k in keys:
+        if k in out:
+            out[k] = out[k].view(torch.bool)
+
+
+def _check_pairs(pairs):
+    pairs = torch.as_tensor(pairs)
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"pairs must be [P,2], got {tuple(pairs.shape)}")
+    return pairs
+
+
+def _pair_inputs(a, name, x, y, mx, my, pairs, max_n=None, nonempty=False):
+    """The pair-work-list family: checks x [Bx,N,3], y [By,N,3], mx [Bx,N], my [By,N], pairs [P,2] (ValueError), N <= max_n
+    (PepflowHipError, before any device work) and, with `nonempty`, that neither side is empty; converts (y is x and my is mx share
+    one buffer) and binds x, y, mx, my, pairs, Bx, By, N, P into `a`.  -> (the tensors to keep alive, device, N, P)"""
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise ValueError(f"x must be [B,N,3], got {tuple(x.shape)}")
+    Bx, N, _ = x.shape
+    By = y.shape[0] if y.dim() == 3 else -1
+    if tuple(y.shape[1:]) != (N, 3) or tuple(mx.shape) != (Bx, N) or tuple(my.shape) != (By, N):
+        raise ValueError(f"shapes do not agree: x {tuple(x.shape)}, y {tuple(y.shape)}, mx {tuple(mx.shape)}, my {tuple(my.shape)}")
+    pairs = _check_pairs(pairs)
+    if max_n is not None and N > max_n:
+        raise _capi.PepflowHipError(f"{name}: N = {N} points exceeds the kernel's bound of {max_n}")
+    if nonempty and (N == 0 or Bx == 0 or By == 0):
+        raise ValueError(f"{name} needs at least one point set of at least one point on each side")
+    dev = x.device
+    kx, kmx = _f32(x, dev), _bytes(mx, dev)
+    keep = [kx, kx if y is x else _f32(y, dev), kmx, kmx if my is mx else _bytes(my, dev), pairs.to(dev, torch.int32).contiguous()]
+    _bind_in(a, x=keep[0], y=keep[1], mx=keep[2], my=keep[3], pairs=keep[4])
+    a.Bx, a.By, a.N, a.P = Bx, By, N, pairs.shape[0]
+    return keep, dev, N, pairs.shape[0]
+
+
+def _within_groups(B, groups):
+    """-> pairs [P,2] int32: every i < j of the same group (all one group when `groups` is None)"""
+    return group_pairs(torch.zeros(B, dtype=torch.int64) if groups is None else groups)[0]
+
+
+def _mirrored(B, pairs, dev, *filled):
+    """one [B,B] matrix per (values [P], diagonal) of `filled`: values at (i, j) and (j, i) of each pair, NaN elsewhere"""
+    i, j = pairs[:, 0].to(dev, torch.int64), pairs[:, 1].to(dev, torch.int64)
+    eye = torch.eye(B, dtype=torch.bool, device=dev)
+    res = []
+    for v, diag in filled:
+        m = torch.full((B, B), float("nan"), device=dev)
+        m[i, j] = v
+        m[j, i] = v
+        res.append(m.masked_fill(eye, diag))
+    return res
+
+
+def _structure(pos, atom_mask, per_residue, max_n=None, tag="", dev=None):
+    """The heavy-atom family: checks pos [B,N,A,3] (A >= 14), atom_mask [B,N,A] and the [B,N] tensors of per_residue = ((name, tensor
+    or None, dtype), ...), and N <= max_n (ValueError); converts pos to float32, atom_mask to bytes and each given tensor to its
+    dtype (uint8: a mask), on `dev` (None: where pos is).
+    -> (device, (B, N, A), pos, atom_mask, [the converted per-residue tensors, None where not given])"""
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 4 or pos.shape[3] != 3 or pos.shape[2] < VIOLATION_SLOTS:
+        raise ValueError(f"{tag}pos must be [B,N,A,3] with A >= {VIOLATION_SLOTS}, got {tuple(getattr(pos, 'shape', ()))}")
+    B, N, A, _ = pos.shape
+    if tuple(atom_mask.shape) != (B, N, A):
+        raise ValueError(f"{tag}atom_mask must be [B,N,A] = {(B, N, A)}, got {tuple(atom_mask.shape)}")
+    for nm, t, _ in per_residue:
+        if t is not None and tuple(t.shape) != (B, N):
+            raise ValueError(f"{tag}{nm} must be [B,N] = {(B, N)}, got {tuple(t.shape)}")
+    if max_n is not None and N > max_n:
+        raise ValueError(f"at most {max_n} residues per structure, got {N}")
+    dev = pos.device if dev is None else dev
+    conv = [None if t is None else _bytes(t, dev) if dt is torch.uint8 else t.to(dev, dt).contiguous() for _, t, dt in per_residue]
+    return dev, (B, N, A), _f32(pos, dev), _bytes(atom_mask, dev), conv
 
 
 def superpose(x, y, mx, my, pairs, aa_x=None, aa_y=None, allow_reflection=False, transform=False, aligned=False):
@@ -36,40 +133,26 @@ def superpose(x, y, mx, my, pairs, aa_x=None, aa_y=None, allow_reflection=False,
     -> dict of device tensors: rmsd_plain, rmsd (proper Kabsch), count, degenerate [P]; ident [P] if aa_x is given; rot [P,3,3],
     trans [P,3] if `transform`; aligned [P,N,3] (rot x[i] + trans for all N points) if `aligned`.  rot / trans / aligned follow
     `allow_reflection` (True: the reference's `align` rotation, which may be a reflection; False: the proper rotation)."""
-    dev = x.device
-    Bx, N, _ = x.shape
-    By = y.shape[0]
-    if y.shape[1:] != (N, 3) or tuple(mx.shape) != (Bx, N) or tuple(my.shape) != (By, N):
-        raise ValueError(f"shapes do not agree: x {tuple(x.shape)}, y {tuple(y.shape)}, mx {tuple(mx.shape)}, my {tuple(my.shape)}")
     if (aa_x is None) != (aa_y is None):
         raise ValueError("aa_x and aa_y go together")
-    keep = [_f32(x, (Bx, N, 3), dev)]
-    keep.append(keep[0] if y is x else _f32(y, (By, N, 3), dev))
-    keep += [_u8(mx, (Bx, N), dev)]
-    keep.append(keep[2] if my is mx else _u8(my, (By, N), dev))
-    pairs = pairs.to(dev, torch.int32).reshape(-1, 2).contiguous()
-    P = pairs.shape[0]
     a = _capi.SuperposeArgs()
-    a.x, a.y, a.mx, a.my = (_capi.dptr(t, t.dtype, nm) for t, nm in zip(keep, ("x", "y", "mx", "my")))
-    a.pairs = _capi.dptr(pairs, torch.int32, "pairs")
+    keep, dev, N, P = _pair_inputs(a, "superpose", x, y, mx, my, pairs)
     out = {"rmsd_plain": torch.empty(P, device=dev), "rmsd": torch.empty(P, device=dev),
            "count": torch.empty(P, dtype=torch.int32, device=dev), "degenerate": torch.empty(P, dtype=torch.uint8, device=dev)}
     if aa_x is not None:
-        keep.append(aa_x.to(dev, torch.int64).reshape(Bx, N).contiguous())
-        keep.append(keep[-1] if aa_y is aa_x else aa_y.to(dev, torch.int64).reshape(By, N).contiguous())
-        a.aa_x, a.aa_y = keep[-2].data_ptr(), keep[-1].data_ptr()
+        keep.append(aa_x.to(dev, torch.int64).reshape(a.Bx, N).contiguous())
+        keep.append(keep[-1] if aa_y is aa_x else aa_y.to(dev, torch.int64).reshape(a.By, N).contiguous())
+        _bind_in(a, aa_x=keep[-2], aa_y=keep[-1])
         out["ident"] = torch.empty(P, device=dev)
     if transform:
         out["rot"], out["trans"] = torch.empty(P, 3, 3, device=dev), torch.empty(P, 3, device=dev)
     if aligned:
         out["aligned"] = torch.empty(P, N, 3, device=dev)
-    for k in ("rmsd_plain", "rmsd", "count", "degenerate", "ident", "rot", "trans", "aligned"):
-        if k in out:
-            setattr(a, k, out[k].data_ptr())
-    a.Bx, a.By, a.N, a.P, a.allow_reflection = Bx, By, N, P, int(bool(allow_reflection))
+    _bind_out(a, out)
+    a.allow_reflection = int(bool(allow_reflection))
     if P:
         _capi.check(_capi.load().pf_superpose_fwd(C.byref(a), _capi.stream_ptr()), "pf_superpose_fwd")
-    out["degenerate"] = out["degenerate"].bool()
+    _as_bool(out, "degenerate")
     return out
 
 
@@ -113,19 +196,11 @@ def pairwise_superpose_rmsd(x, mask, aa=None, groups=None):
     is None), mirrored, so the matrix is exactly symmetric with an exact-zero diagonal; pairs across groups are NaN.
     With `aa` [B,N] -> (rmsd, ident [B,B]): the fraction of the shared points with the same residue type (diagonal 1)."""
     B = x.shape[0]
-    dev = x.device
-    pairs, _, _ = group_pairs(torch.zeros(B, dtype=torch.int64) if groups is None else groups)
+    pairs = _within_groups(B, groups)
     out = superpose(x, x, mask, mask, pairs, aa_x=aa, aa_y=aa)
-    i, j = pairs[:, 0].to(dev, torch.int64), pairs[:, 1].to(dev, torch.int64)
-    eye = torch.eye(B, dtype=torch.bool, device=dev)
-
-    def mirror(v, diag):
-        m = torch.full((B, B), float("nan"), device=dev)
-        m[i, j] = v
-        m[j, i] = v
-        return m.masked_fill(eye, diag)
-    rmsd = mirror(out["rmsd"], 0.0)
-    return rmsd if aa is None else (rmsd, mirror(out["ident"], 1.0))
+    if aa is None:
+        return _mirrored(B, pairs, x.device, (out["rmsd"], 0.0))[0]
+    return tuple(_mirrored(B, pairs, x.device, (out["rmsd"], 0.0), (out["ident"], 1.0)))
 
 
 TM_MAX_N = 512              # PF_TM_MAX_N: the longest point set pf_tm_score_fwd takes
@@ -140,44 +215,19 @@ def tm_score(x, y, mx, my, pairs, transform=False, aligned=False):
     -> dict of device tensors: tm [P] (NaN where fewer than 3 points are shared), count [P] (shared points; 0 for pair indices out
     of range), lnorm [P] (the normalising count); rot [P,3,3], trans [P,3] of the best superposition (y ~ rot x + trans, a proper
     rotation) if `transform`; aligned [P,N,3] (rot x[i] + trans for all N points) if `aligned`."""
-    if x.dim() != 3 or x.shape[2] != 3:
-        raise ValueError(f"x must be [B,N,3], got {tuple(x.shape)}")
-    Bx, N, _ = x.shape
-    By = y.shape[0] if y.dim() == 3 else -1
-    if tuple(y.shape[1:]) != (N, 3) or tuple(mx.shape) != (Bx, N) or tuple(my.shape) != (By, N):
-        raise ValueError(f"shapes do not agree: x {tuple(x.shape)}, y {tuple(y.shape)}, mx {tuple(mx.shape)}, my {tuple(my.shape)}")
-    pairs = torch.as_tensor(pairs)
-    if pairs.dim() != 2 or pairs.shape[1] != 2:
-        raise ValueError(f"pairs must be [P,2], got {tuple(pairs.shape)}")
-    if N > TM_MAX_N:
-        raise _capi.PepflowHipError(f"tm_score: N = {N} points exceeds the kernel's bound of {TM_MAX_N}")
-    if N == 0 or Bx == 0 or By == 0:
-        raise ValueError("tm_score needs at least one point set of at least one point on each side")
-    dev = x.device
-    keep = [_f32(x, (Bx, N, 3), dev)]
-    keep.append(keep[0] if y is x else _f32(y, (By, N, 3), dev))
-    keep += [_u8(mx, (Bx, N), dev)]
-    keep.append(keep[2] if my is mx else _u8(my, (By, N), dev))
-    pairs = pairs.to(dev, torch.int32).contiguous()
-    P = pairs.shape[0]
     a = _capi.TmScoreArgs()
-    a.x, a.y, a.mx, a.my = (_capi.dptr(t, t.dtype, nm) for t, nm in zip(keep, ("x", "y", "mx", "my")))
-    a.pairs = _capi.dptr(pairs, torch.int32, "pairs")
+    keep, dev, N, P = _pair_inputs(a, "tm_score", x, y, mx, my, pairs, max_n=TM_MAX_N, nonempty=True)
     out = {"tm": torch.empty(P, device=dev), "count": torch.empty(P, dtype=torch.int32, device=dev),
            "lnorm": torch.empty(P, dtype=torch.int32, device=dev)}
     if transform:
         out["rot"], out["trans"] = torch.empty(P, 3, 3, device=dev), torch.empty(P, 3, device=dev)
     if aligned:
         out["aligned"] = torch.empty(P, N, 3, device=dev)
-    for k in ("tm", "count", "lnorm", "rot", "trans", "aligned"):
-        if k in out:
-            setattr(a, k, out[k].data_ptr())
-    a.Bx, a.By, a.N, a.P = Bx, By, N, P
+    _bind_out(a, out)
     if P:
         lib = _capi.load()
-        slots = lib.pf_tm_score_work_slots(N)
-        work = torch.empty(P * slots * TM_SLOT_BYTES, dtype=torch.uint8, device=dev)
-        a.work = work.data_ptr()
+        keep.append(torch.empty(P * lib.pf_tm_score_work_slots(N) * TM_SLOT_BYTES, dtype=torch.uint8, device=dev))
+        a.work = keep[-1].data_ptr()
         _capi.check(lib.pf_tm_score_fwd(C.byref(a), _capi.stream_ptr()), "pf_tm_score_fwd")
     return out
 
@@ -187,14 +237,8 @@ def pairwise_tm_score(x, mask, groups=None):
     onto x[j] normalised by mask[j], mirrored, so the matrix is exactly symmetric with a diagonal of 1; pairs across groups are NaN.
     Within a group of one complex the masks are equal and the score does not depend on the direction."""
     B = x.shape[0]
-    dev = x.device
-    pairs, _, _ = group_pairs(torch.zeros(B, dtype=torch.int64) if groups is None else groups)
-    tm = tm_score(x, x, mask, mask, pairs)["tm"]
-    i, j = pairs[:, 0].to(dev, torch.int64), pairs[:, 1].to(dev, torch.int64)
-    m = torch.full((B, B), float("nan"), device=dev)
-    m[i, j] = tm
-    m[j, i] = tm
-    return m.masked_fill(torch.eye(B, dtype=torch.bool, device=dev), 1.0)
+    pairs = _within_groups(B, groups)
+    return _mirrored(B, pairs, x.device, (tm_score(x, x, mask, mask, pairs)["tm"], 1.0))[0]
 
 
 TM_ALIGN_MAX_N = 512        # PF_TM_ALIGN_MAX_N: the most slots pf_tm_align_fwd takes
@@ -220,31 +264,10 @@ def tm_align(x, y, mx, my, pairs, transform=False, alignment=False, aligned=Fals
                       whether the pair counts in n_aligned; seqxA / seqyA follow from y2x;
       aligned [P,N,3] (`aligned`): rot x + trans for all N points.
     NaN scores where a chain has fewer than 3 residues or the pair indices are out of range (n_aligned 0)."""
-    if x.dim() != 3 or x.shape[2] != 3:
-        raise ValueError(f"x must be [B,N,3], got {tuple(x.shape)}")
-    Bx, N, _ = x.shape
-    By = y.shape[0] if y.dim() == 3 else -1
-    if tuple(y.shape[1:]) != (N, 3) or tuple(mx.shape) != (Bx, N) or tuple(my.shape) != (By, N):
-        raise ValueError(f"shapes do not agree: x {tuple(x.shape)}, y {tuple(y.shape)}, mx {tuple(mx.shape)}, my {tuple(my.shape)}")
-    pairs = torch.as_tensor(pairs)
-    if pairs.dim() != 2 or pairs.shape[1] != 2:
-        raise ValueError(f"pairs must be [P,2], got {tuple(pairs.shape)}")
-    if N > TM_ALIGN_MAX_N:
-        raise _capi.PepflowHipError(f"tm_align: N = {N} points exceeds the kernel's bound of {TM_ALIGN_MAX_N}")
-    if N == 0 or Bx == 0 or By == 0:
-        raise ValueError("tm_align needs at least one chain of at least one point on each side")
     if max_len is not None and not (0 <= int(max_len)):
         raise ValueError(f"max_len must be >= 0, got {max_len}")
-    dev = x.device
-    keep = [_f32(x, (Bx, N, 3), dev)]
-    keep.append(keep[0] if y is x else _f32(y, (By, N, 3), dev))
-    keep += [_u8(mx, (Bx, N), dev)]
-    keep.append(keep[2] if my is mx else _u8(my, (By, N), dev))
-    pairs = pairs.to(dev, torch.int32).contiguous()
-    P = pairs.shape[0]
     a = _capi.TmAlignArgs()
-    a.x, a.y, a.mx, a.my = (_capi.dptr(t, t.dtype, nm) for t, nm in zip(keep, ("x", "y", "mx", "my")))
-    a.pairs = _capi.dptr(pairs, torch.int32, "pairs")
+    keep, dev, N, P = _pair_inputs(a, "tm_align", x, y, mx, my, pairs, max_n=TM_ALIGN_MAX_N, nonempty=True)
     out = {"tm": torch.empty(P, device=dev), "tm_x": torch.empty(P, device=dev), "rmsd": torch.empty(P, device=dev)}
     for k in ("n_aligned", "len_x", "len_y"):
         out[k] = torch.empty(P, dtype=torch.int32, device=dev)
@@ -254,15 +277,11 @@ def tm_align(x, y, mx, my, pairs, transform=False, alignment=False, aligned=Fals
         out["y2x"], out["kept"] = torch.empty(P, N, dtype=torch.int32, device=dev), torch.empty(P, N, dtype=torch.uint8, device=dev)
     if aligned:
         out["aligned"] = torch.empty(P, N, 3, device=dev)
-    for k in ("tm", "tm_x", "rmsd", "n_aligned", "len_x", "len_y", "rot", "trans", "y2x", "kept", "aligned"):
-        if k in out:
-            setattr(a, k, out[k].data_ptr())
-    a.Bx, a.By, a.N, a.P = Bx, By, N, P
+    _bind_out(a, out)
     a.max_len = 0 if max_len is None else min(int(max_len), N)
     if P:
         _capi.check(_capi.load().pf_tm_align_fwd(C.byref(a), _capi.stream_ptr()), "pf_tm_align_fwd")
-    if alignment:
-        out["kept"] = out["kept"].bool()
+    _as_bool(out, "kept")
     return out
 
 
@@ -271,23 +290,15 @@ def pairwise_tm_align(x, mask, groups=None):
     onto x[j], normalised by chain j's length, mirrored as pairwise_tm_score is, with a diagonal of 1; pairs across groups are NaN.
     Unlike the fixed-correspondence TM-score, TM-align's score may depend on the direction; the i-onto-j one is kept."""
     B = x.shape[0]
-    dev = x.device
-    pairs, _, _ = group_pairs(torch.zeros(B, dtype=torch.int64) if groups is None else groups)
+    pairs = _within_groups(B, groups)
     max_len = int(torch.as_tensor(mask).bool().sum(1).max()) if B else 0
-    tm = tm_align(x, x, mask, mask, pairs, max_len=max_len)["tm"]
-    i, j = pairs[:, 0].to(dev, torch.int64), pairs[:, 1].to(dev, torch.int64)
-    m = torch.full((B, B), float("nan"), device=dev)
-    m[i, j] = tm
-    m[j, i] = tm
-    return m.masked_fill(torch.eye(B, dtype=torch.bool, device=dev), 1.0)
+    return _mirrored(B, pairs, x.device, (tm_align(x, x, mask, mask, pairs, max_len=max_len)["tm"], 1.0))[0]
 
 
 DSSP_MAX_N = 512            # PF_DSSP_MAX_N: the longest chain slot pf_dssp_fwd takes
 SS_SYMBOLS = "HBEGITS-"     # 8-state codes 0..7: SSTRUCT_SYMB_TO_INDEX of pepflow/modules/protein/dssp.py
 SS_SIMPLE = "HEC"           # simplified codes 0..2 (mdtraj's compute_dssp(simplified=True))
 SS_MASKED = 255
-# 8-state -> simplified: H, G, I -> 0 'H'; E, B -> 1 'E'; T, S, '-' -> 2 'C'; anything else (255 masked) -> 255
-_SIMPLIFY = {}
 
 
 def dssp(pos, mask, chain=None, aa=None, hbonds=False):
@@ -310,15 +321,9 @@ def dssp(pos, mask, chain=None, aa=None, hbonds=False):
     if N > DSSP_MAX_N:
         raise ValueError(f"dssp: N = {N} residues exceeds the kernel's bound of {DSSP_MAX_N}")
     dev = pos.device
-    keep = [pos.to(dev, torch.float32).contiguous(), _u8(mask, (B, N), dev)]
+    keep = [_f32(pos, dev), _bytes(mask, dev)] + [None if t is None else t.to(dev, torch.int64).contiguous() for t in (chain, aa)]
     a = _capi.DsspArgs()
-    a.pos, a.mask = _capi.dptr(keep[0], torch.float32, "pos"), _capi.dptr(keep[1], torch.uint8, "mask")
-    if chain is not None:
-        keep.append(chain.to(dev, torch.int64).contiguous())
-        a.chain = keep[-1].data_ptr()
-    if aa is not None:
-        keep.append(aa.to(dev, torch.int64).contiguous())
-        a.aa = keep[-1].data_ptr()
+    _bind_in(a, pos=keep[0], mask=keep[1], chain=keep[2], aa=keep[3])
     ss = torch.empty(B, N, dtype=torch.uint8, device=dev)
     a.ss = ss.data_ptr()
     if hbonds:
@@ -337,12 +342,11 @@ def _proline():
 
 def ss_simplify(ss):
     """8-state codes -> mdtraj's simplified ones: 0 'H' (H, G, I), 1 'E' (E, B), 2 'C' (T, S, '-'); 255 stays 255"""
-    key = str(ss.device)
-    if key not in _SIMPLIFY:
+    def make():             # H, G, I -> 0 'H'; E, B -> 1 'E'; T, S, '-' -> 2 'C'; anything else (255 masked) -> 255
         t = torch.full((256,), SS_MASKED, dtype=torch.uint8)
         t[:8] = torch.tensor([0, 1, 1, 0, 0, 2, 2, 2], dtype=torch.uint8)
-        _SIMPLIFY[key] = t.to(ss.device)
-    return _SIMPLIFY[key][ss.long()]
+        return t
+    return _table("ss_simplify", ss.device, make)[ss.long()]
 
 
 def ss_strings(ss, simplified=False):
@@ -359,7 +363,6 @@ def ss_strings(ss, simplified=False):
 VDW_RADIUS = {"C": 1.7, "N": 1.55, "O": 1.52, "S": 1.8}    # openfold/np/residue_constants.py van_der_waals_radius
 VIOLATION_SLOTS = 14
 _UNK_ELEMENTS = "NCCO"          # a residue type >= 20: N, CA, C, O only
-_RADIUS = {}
 
 
 def vdw_radius_table():
@@ -393,30 +396,11 @@ def structural_violations(pos, atom_mask, aa, residue_index, query=None, group=N
     clash_mean_loss [B]; with `group` clash_atom_loss_cross, clash_atom_cross; bond_c_n_loss_mean, angle_ca_c_n_loss_mean,
     angle_c_n_ca_loss_mean [B]; connection_loss [B,N]; connection_violation [B,N] bool; ca_ca_break [B,N] bool (connection
     (n, n + 1) at n); ca_ca_extreme [B]."""
-    if not isinstance(pos, torch.Tensor) or pos.dim() != 4 or pos.shape[3] != 3 or pos.shape[2] < VIOLATION_SLOTS:
-        raise ValueError(f"pos must be [B,N,A,3] with A >= {VIOLATION_SLOTS}, got {tuple(getattr(pos, 'shape', ()))}")
-    B, N, A, _ = pos.shape
-    if tuple(atom_mask.shape) != (B, N, A):
-        raise ValueError(f"atom_mask must be [B,N,A] = {(B, N, A)}, got {tuple(atom_mask.shape)}")
-    for nm, t in (("aa", aa), ("residue_index", residue_index), ("query", query), ("group", group)):
-        if t is not None and tuple(t.shape) != (B, N):
-            raise ValueError(f"{nm} must be [B,N] = {(B, N)}, got {tuple(t.shape)}")
-    dev = pos.device
-    key = str(dev)
-    keep = [pos.to(dev, torch.float32).contiguous(), atom_mask.to(dev).to(torch.uint8).contiguous(),
-            aa.to(dev, torch.int64).contiguous(), residue_index.to(dev, torch.int32).contiguous()]
+    dev, (B, N, A), pos, atom_mask, (aa, residue_index, query, group) = _structure(pos, atom_mask, (
+        ("aa", aa, torch.int64), ("residue_index", residue_index, torch.int32), ("query", query, torch.uint8), ("group", group, torch.uint8)))
     a = _capi.ViolationsArgs()
-    a.pos, a.atom_mask = _capi.dptr(keep[0], torch.float32, "pos"), _capi.dptr(keep[1], torch.uint8, "atom_mask")
-    a.aa, a.residue_index = _capi.dptr(keep[2], torch.int64, "aa"), _capi.dptr(keep[3], torch.int32, "residue_index")
-    if key not in _RADIUS:
-        _RADIUS[key] = vdw_radius_table().contiguous().to(dev)
-    a.radius = _RADIUS[key].data_ptr()
-    if query is not None:
-        keep.append(_u8(query, (B, N), dev))
-        a.query = keep[-1].data_ptr()
-    if group is not None:
-        keep.append(_u8(group, (B, N), dev))
-        a.group = keep[-1].data_ptr()
+    _bind_in(a, pos=pos, atom_mask=atom_mask, aa=aa, residue_index=residue_index, query=query, group=group)
+    a.radius = _table("vdw_radius", dev, vdw_radius_table).data_ptr()
     S = VIOLATION_SLOTS
     f32 = lambda *shape: torch.empty(*shape, device=dev)  # noqa: E731
     u8 = lambda *shape: torch.empty(*shape, dtype=torch.uint8, device=dev)  # noqa: E731
@@ -426,8 +410,7 @@ def structural_violations(pos, atom_mask, aa, residue_index, query=None, group=N
         out.update(clash_atom_loss_cross=f32(B, N, S), clash_atom_cross=u8(B, N, S))
     out.update(bond_c_n_loss_mean=f32(B), angle_ca_c_n_loss_mean=f32(B), angle_c_n_ca_loss_mean=f32(B), connection_loss=f32(B, N),
                connection_violation=u8(B, N), ca_ca_break=u8(B, N), ca_ca_extreme=f32(B))
-    for k, v in out.items():
-        setattr(a, k, v.data_ptr())
+    _bind_out(a, out)
     a.B, a.N, a.n_atoms, a.pro = B, N, A, _proline()
     a.violation_tolerance_factor, a.clash_overlap_tolerance = float(violation_tolerance_factor), float(clash_overlap_tolerance)
     if B and N:
@@ -435,15 +418,12 @@ def structural_violations(pos, atom_mask, aa, residue_index, query=None, group=N
     else:
         for v in out.values():
             v.zero_()
-    for k in ("clash_atom", "clash_atom_cross", "connection_violation", "ca_ca_break"):
-        if k in out:
-            out[k] = out[k].bool()
+    _as_bool(out, "clash_atom", "clash_atom_cross", "connection_violation", "ca_ca_break")
     return out
 
 
 SASA_SLOTS = 15
 SASA_MAX_POINTS, SASA_MAX_N = 1024, 512
-_SASA_RADIUS, _SASA_POINTS = {}, {}
 
 
 def sasa_radius_table():
@@ -477,50 +457,27 @@ def sasa(pos, atom_mask, aa, query=None, group=None, probe_radius=1.4, n_points=
     on its own, so sasa_*_own - sasa_* is the area buried by the other group.
     -> dict of device tensors: count [B,N,15] int32 accessible points, sasa_atom [B,N,15] float32 = 4 pi (radius + probe)^2 count /
     n_points, sasa_residue [B,N], sasa_total [B]; with `group` count_own, sasa_atom_own, sasa_residue_own, sasa_total_own."""
-    if not isinstance(pos, torch.Tensor) or pos.dim() != 4 or pos.shape[3] != 3 or pos.shape[2] < VIOLATION_SLOTS:
-        raise ValueError(f"pos must be [B,N,A,3] with A >= {VIOLATION_SLOTS}, got {tuple(getattr(pos, 'shape', ()))}")
-    B, N, A, _ = pos.shape
-    if tuple(atom_mask.shape) != (B, N, A):
-        raise ValueError(f"atom_mask must be [B,N,A] = {(B, N, A)}, got {tuple(atom_mask.shape)}")
-    for nm, t in (("aa", aa), ("query", query), ("group", group)):
-        if t is not None and tuple(t.shape) != (B, N):
-            raise ValueError(f"{nm} must be [B,N] = {(B, N)}, got {tuple(t.shape)}")
-    if N > SASA_MAX_N:
-        raise ValueError(f"at most {SASA_MAX_N} residues per structure, got {N}")
     points = sphere_points(n_points)                # checks n_points
     probe_radius = float(probe_radius)
     if not 0.0 <= probe_radius < 1e6:
         raise ValueError(f"probe_radius must be >= 0, got {probe_radius}")
-    dev = pos.device
-    key = str(dev)
-    keep = [pos.to(dev, torch.float32).contiguous(), atom_mask.to(dev).to(torch.uint8).contiguous(),
-            aa.to(dev, torch.int64).contiguous()]
+    dev, (B, N, A), pos, atom_mask, (aa, query, group) = _structure(pos, atom_mask, (
+        ("aa", aa, torch.int64), ("query", query, torch.uint8), ("group", group, torch.uint8)), max_n=SASA_MAX_N)
     a = _capi.SasaArgs()
-    a.pos, a.atom_mask = _capi.dptr(keep[0], torch.float32, "pos"), _capi.dptr(keep[1], torch.uint8, "atom_mask")
-    a.aa = _capi.dptr(keep[2], torch.int64, "aa")
-    if key not in _SASA_RADIUS:
-        _SASA_RADIUS[key] = sasa_radius_table().contiguous().to(dev)
-    if (key, n_points) not in _SASA_POINTS:
-        _SASA_POINTS[key, n_points] = points.contiguous().to(dev)
-    a.radius, a.points = _SASA_RADIUS[key].data_ptr(), _SASA_POINTS[key, n_points].data_ptr()
-    if query is not None:
-        keep.append(_u8(query, (B, N), dev))
-        a.query = keep[-1].data_ptr()
-    if group is not None:
-        keep.append(_u8(group, (B, N), dev))
-        a.group = keep[-1].data_ptr()
+    _bind_in(a, pos=pos, atom_mask=atom_mask, aa=aa, query=query, group=group)
+    a.radius = _table("sasa_radius", dev, sasa_radius_table).data_ptr()
+    a.points = _table("sphere_points", dev, lambda: points, n_points).data_ptr()
     S = SASA_SLOTS
     f32 = lambda *shape: torch.empty(*shape, device=dev)  # noqa: E731
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)  # noqa: E731
     out = {"count": i32(B, N, S), "sasa_atom": f32(B, N, S), "sasa_residue": f32(B, N), "sasa_total": f32(B)}
     if group is not None:
         out.update(count_own=i32(B, N, S), sasa_atom_own=f32(B, N, S), sasa_residue_own=f32(B, N), sasa_total_own=f32(B))
-    for k, v in out.items():
-        setattr(a, k, v.data_ptr())
+    _bind_out(a, out)
     a.B, a.N, a.n_atoms, a.n_points, a.probe_radius = B, N, A, n_points, probe_radius
     if B and N:
-        keep.append(f32(B, N, 4))                   # the residue-sized workspace: centre and padded extent
-        a.work = keep[-1].data_ptr()
+        work = f32(B, N, 4)                         # the residue-sized workspace: centre and padded extent
+        a.work = work.data_ptr()
         _capi.check(_capi.load().pf_sasa_fwd(C.byref(a), _capi.stream_ptr()), "pf_sasa_fwd")
     else:
         for v in out.values():
@@ -534,7 +491,6 @@ TORSION_NAMES = ("omega", "phi", "psi", "psi_o", "chi1", "chi2", "chi3", "chi4")
 PI_PERIODIC_CHI = {"ASP": 2, "GLU": 3, "PHE": 2, "TYR": 2}
 EQUIVALENT_ATOMS = {"ASP": (("OD1", "OD2"),), "GLU": (("OE1", "OE2"),), "PHE": (("CD1", "CD2"), ("CE1", "CE2")),
                     "TYR": (("CD1", "CD2"), ("CE1", "CE2"))}
-_TORSION_TABLES = {}
 
 
 def chi_atom_table():
@@ -565,19 +521,6 @@ def swap_table():
     return tab
 
 
-def _bytes(t, dev):
-    """a mask as uint8 on the device; a bool tensor is reinterpreted, not copied"""
-    t = t.to(dev)
-    return (t.view(torch.uint8) if t.dtype == torch.bool else t.to(torch.uint8)).contiguous()
-
-
-def _torsion_tables(dev):
-    key = str(dev)
-    if key not in _TORSION_TABLES:
-        _TORSION_TABLES[key] = (chi_atom_table().to(dev), pi_periodic_table().to(torch.uint8).to(dev), swap_table().to(dev))
-    return _TORSION_TABLES[key]
-
-
 def torsion_angles(pos, atom_mask, aa, residue_index=None):
     """pf_torsions_fwd: the torsion angles of heavy-atom structures (conventions: csrc/torsions.hip).
 
@@ -588,30 +531,18 @@ def torsion_angles(pos, atom_mask, aa, residue_index=None):
     psi_o (N, CA, C, O: slot 0 of preprocess.get_torsion_angle; on coordinates rebuilt by full_atom it is the model's first angle
     + pi), chi1..chi4; defined [B,N,8] bool: all four atoms in atom_mask, the neighbour bonded (backbone angles), the type has the chi,
     no degenerate geometry.  Undefined angles are 0, never NaN."""
-    if not isinstance(pos, torch.Tensor) or pos.dim() != 4 or pos.shape[3] != 3 or pos.shape[2] < VIOLATION_SLOTS:
-        raise ValueError(f"pos must be [B,N,A,3] with A >= {VIOLATION_SLOTS}, got {tuple(getattr(pos, 'shape', ()))}")
-    B, N, A, _ = pos.shape
-    if tuple(atom_mask.shape) != (B, N, A):
-        raise ValueError(f"atom_mask must be [B,N,A] = {(B, N, A)}, got {tuple(atom_mask.shape)}")
-    for nm, t in (("aa", aa), ("residue_index", residue_index)):
-        if t is not None and tuple(t.shape) != (B, N):
-            raise ValueError(f"{nm} must be [B,N] = {(B, N)}, got {tuple(t.shape)}")
-    dev = pos.device
-    keep = [pos.to(dev, torch.float32).contiguous(), _bytes(atom_mask, dev), aa.to(dev, torch.int64).contiguous()]
+    dev, (B, N, A), pos, atom_mask, (aa, residue_index) = _structure(pos, atom_mask, (
+        ("aa", aa, torch.int64), ("residue_index", residue_index, torch.int32)))
     a = _capi.TorsionsArgs()
-    a.pos, a.atom_mask = _capi.dptr(keep[0], torch.float32, "pos"), _capi.dptr(keep[1], torch.uint8, "atom_mask")
-    a.aa = _capi.dptr(keep[2], torch.int64, "aa")
-    if residue_index is not None:
-        keep.append(residue_index.to(dev, torch.int32).contiguous())
-        a.residue_index = keep[-1].data_ptr()
-    a.chi_atoms = _torsion_tables(dev)[0].data_ptr()
-    angles = torch.empty(B, N, 8, device=dev)
-    defined = torch.empty(B, N, 8, dtype=torch.uint8, device=dev)
-    a.angles, a.defined = angles.data_ptr(), defined.data_ptr()
+    _bind_in(a, pos=pos, atom_mask=atom_mask, aa=aa, residue_index=residue_index)
+    a.chi_atoms = _table("chi_atoms", dev, chi_atom_table).data_ptr()
+    out = {"angles": torch.empty(B, N, 8, device=dev), "defined": torch.empty(B, N, 8, dtype=torch.uint8, device=dev)}
+    _bind_out(a, out)
     a.B, a.N, a.n_atoms = B, N, A
     if B and N:
         _capi.check(_capi.load().pf_torsions_fwd(C.byref(a), _capi.stream_ptr()), "pf_torsions_fwd")
-    return {"angles": angles, "defined": defined.view(torch.bool)}
+    _as_bool(out, "defined")
+    return out
 
 
 _COMPARE_KEYS = ("pos", "atom_mask", "aa", "angles", "defined")
@@ -632,22 +563,7 @@ def sidechain_compare(x, y, pairs, correct_tol=math.radians(20), per_residue=Fal
     for nm, d in (("x", x), ("y", y)):
         if not isinstance(d, dict) or any(k not in d for k in _COMPARE_KEYS):
             raise ValueError(f"{nm} must be a dict with {_COMPARE_KEYS}")
-        pos = d["pos"]
-        if not isinstance(pos, torch.Tensor) or pos.dim() != 4 or pos.shape[3] != 3 or pos.shape[2] < VIOLATION_SLOTS:
-            raise ValueError(f"{nm}['pos'] must be [B,N,A,3] with A >= {VIOLATION_SLOTS}, got {tuple(getattr(pos, 'shape', ()))}")
-        B, N, A, _ = pos.shape
-        for k, shape in (("atom_mask", (B, N, A)), ("aa", (B, N)), ("angles", (B, N, 8)), ("defined", (B, N, 8))):
-            if tuple(d[k].shape) != shape:
-                raise ValueError(f"{nm}[{k!r}] must be {shape}, got {tuple(d[k].shape)}")
-    Bx, N, Ax, _ = x["pos"].shape
-    By, Ny, Ay, _ = y["pos"].shape
-    if Ny != N:
-        raise ValueError(f"x and y must have the same number of residues, got {N} and {Ny}")
-    if N == 0 or Bx == 0 or By == 0:
-        raise ValueError("sidechain_compare needs at least one structure of at least one residue on each side")
-    pairs = torch.as_tensor(pairs)
-    if pairs.dim() != 2 or pairs.shape[1] != 2:
-        raise ValueError(f"pairs must be [P,2], got {tuple(pairs.shape)}")
+    pairs = _check_pairs(pairs)
     correct_tol = float(correct_tol)
     if not 0.0 <= correct_tol <= math.pi:
         raise ValueError(f"correct_tol must be in [0, pi] radians, got {correct_tol}")
@@ -656,21 +572,25 @@ def sidechain_compare(x, y, pairs, correct_tol=math.radians(20), per_residue=Fal
     def aligned(t, n):      # the kernel reads angles as float4 and defined 8 bytes at a time: a view at an odd offset is copied
         return t if t.data_ptr() % n == 0 else t.clone()
 
-    def side(d):
-        return [d["pos"].to(dev, torch.float32).contiguous(), _bytes(d["atom_mask"], dev), d["aa"].to(dev, torch.int64).contiguous(),
-                aligned(d["angles"].to(dev, torch.float32).contiguous(), 16), aligned(_bytes(d["defined"], dev), 8)]
-    kx = side(x)
-    ky = kx if y is x else side(y)
+    def side(d, nm):
+        _, (B, N, A), pos, atom_mask, (aa,) = _structure(d["pos"], d["atom_mask"], (("aa", d["aa"], torch.int64),), tag=nm + ".", dev=dev)
+        for k in ("angles", "defined"):
+            if tuple(d[k].shape) != (B, N, 8):
+                raise ValueError(f"{nm}.{k} must be {(B, N, 8)}, got {tuple(d[k].shape)}")
+        return (B, N, A), dict(pos=pos, mask=atom_mask, aa=aa, angles=aligned(_f32(d["angles"], dev), 16),
+                               defined=aligned(_bytes(d["defined"], dev), 8))
+    (Bx, N, Ax), kx = side(x, "x")
+    (By, Ny, Ay), ky = ((Bx, N, Ax), kx) if y is x else side(y, "y")
+    if Ny != N:
+        raise ValueError(f"x and y must have the same number of residues, got {N} and {Ny}")
+    if N == 0 or Bx == 0 or By == 0:
+        raise ValueError("sidechain_compare needs at least one structure of at least one residue on each side")
     pairs = pairs.to(dev, torch.int32).contiguous()
     P = pairs.shape[0]
     a = _capi.SidechainCompareArgs()
-    for tag, kk in (("x", kx), ("y", ky)):
-        for name, t, dt in zip(("pos", "mask", "aa", "angles", "defined"), kk,
-                               (torch.float32, torch.uint8, torch.int64, torch.float32, torch.uint8)):
-            setattr(a, f"{name}_{tag}", _capi.dptr(t, dt, f"{tag}.{name}"))
-    a.pairs = _capi.dptr(pairs, torch.int32, "pairs")
-    tabs = _torsion_tables(dev)
-    a.periodic, a.swap = tabs[1].data_ptr(), tabs[2].data_ptr()
+    _bind_in(a, pairs=pairs, **{f"{k}_x": t for k, t in kx.items()}, **{f"{k}_y": t for k, t in ky.items()})
+    a.periodic = _table("pi_periodic", dev, lambda: pi_periodic_table().to(torch.uint8)).data_ptr()
+    a.swap = _table("swap", dev, swap_table).data_ptr()
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)  # noqa: E731
     out = {"err_sum": torch.empty(P, 8, dtype=torch.float64, device=dev), "err_count": i32(P, 8), "within": i32(P, 8),
            "res_with_chi": i32(P), "res_correct": i32(P), "sc_sq_sum": torch.empty(P, dtype=torch.float64, device=dev),
@@ -678,11 +598,9 @@ def sidechain_compare(x, y, pairs, correct_tol=math.radians(20), per_residue=Fal
     if per_residue:
         out.update(err=torch.empty(P, N, 8, device=dev), sc_sq=torch.empty(P, N, device=dev), sc_n=i32(P, N),
                    swapped=torch.empty(P, N, dtype=torch.uint8, device=dev))
-    for k, v in out.items():
-        setattr(a, k, v.data_ptr())
+    _bind_out(a, out)
     a.Bx, a.By, a.N, a.P, a.n_atoms_x, a.n_atoms_y, a.correct_tol = Bx, By, N, P, Ax, Ay, correct_tol
     if P:
         _capi.check(_capi.load().pf_sidechain_compare_fwd(C.byref(a), _capi.stream_ptr()), "pf_sidechain_compare_fwd")
-    if per_residue:
-        out["swapped"] = out["swapped"].view(torch.bool)
+    _as_bool(out, "swapped")
     return out

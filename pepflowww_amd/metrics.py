@@ -45,6 +45,39 @@ def _device(*ts):
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def _group_sum(values, index, G, dtype=torch.float64):
+    """values [n, ...] summed into G rows by index [n]; a mean is the quotient of two of these (0 / 0: NaN for an empty group)"""
+    return torch.zeros((G,) + tuple(values.shape[1:]), dtype=dtype, device=values.device).index_add_(0, index, values.to(dtype))
+
+
+def _check_backbone(backbone):
+    if backbone not in ("full_atom", "frames"):
+        raise ValueError(f"backbone must be 'full_atom' or 'frames', got {backbone!r}")
+
+
+def _complexes(final, batch, backbone="full_atom", index=False):
+    """The two complexes the structure metrics compare.  The sample: generated residues rebuilt from the final state -- backbone
+    "full_atom": all heavy atoms (reconstruct_sample: rotmats, trans, angles, seqs), "frames": N, CA, C, O (reconstruct_sample_bb) --
+    with the context kept, types where(generate, seqs, seqs_1).  The native: pos_heavyatom / mask_heavyatom / seqs_1.
+    `backbone` is checked before final / batch are touched.
+    -> (device, res_mask, gen = generate_mask & res_mask, `residue_index` of the batch if `index` else None,
+        (pos_s, mask_s, aa_s), (pos_n, mask_n, seqs_1))"""
+    _check_backbone(backbone)
+    dev = _device(batch["generate_mask"], final["trans"], batch["pos_heavyatom"])
+    res_mask = batch["res_mask"].to(dev).bool()
+    gen = batch["generate_mask"].to(dev).bool() & res_mask
+    rotmats, trans, seqs, seqs_1 = (final[k].to(dev) for k in ("rotmats", "trans", "seqs", "seqs_1"))
+    pos_n, mask_n = batch["pos_heavyatom"].to(dev), batch["mask_heavyatom"].to(dev).bool()
+    if backbone == "full_atom":
+        pos_s, mask_s = full_atom.reconstruct_sample(rotmats, trans, final["angles"].to(dev), seqs, gen, pos_n)
+        mask_s = torch.where(gen[:, :, None], mask_s, mask_n[:, :, :15])
+    else:
+        pos_s, mask_s = full_atom.reconstruct_sample_bb(rotmats, trans, seqs, batch["chain_nb"].to(dev), batch["res_nb"].to(dev),
+                                                        res_mask, gen, pos_n, mask_n)
+    idx = residue_index(batch["chain_nb"].to(dev), batch["res_nb"].to(dev), res_mask) if index else None
+    return dev, res_mask, gen, idx, (pos_s, mask_s, torch.where(gen, seqs, seqs_1)), (pos_n, mask_n, seqs_1)
+
+
 def binding_site(ctx_pos, ctx_atom_mask, res_mask, gen_mask, pep_sample, pep_native, cutoff=BIND_CUTOFF, ca_atom=CA_ATOM):
     """pf_binding_site_fwd -> (site_sample [B,L] bool, site_native [B,L] bool, bsr [B])."""
     B, L, A, _ = ctx_pos.shape
@@ -97,9 +130,9 @@ def evaluate_samples(final, batch, groups=None):
     div = superpose(final["trans"], final["trans"], gen, gen, pairs, aa_x=final["seqs"], aa_y=final["seqs"])
     G = glab.numel()
     gidx = gidx.to(dev)
-    npair = torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, torch.ones_like(gidx, dtype=torch.float64))
-    div_rmsd = torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, div["rmsd"].double()) / npair
-    div_seq = 1.0 - torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, div["ident"].double()) / npair
+    npair = _group_sum(torch.ones_like(gidx), gidx, G)
+    div_rmsd = _group_sum(div["rmsd"], gidx, G) / npair
+    div_seq = 1.0 - _group_sum(div["ident"], gidx, G) / npair
 
     s_site, n_site, bsr = binding_site(batch["pos_heavyatom"], batch["mask_heavyatom"], batch["res_mask"], gen, final["trans"],
                                        final["trans_1"])
@@ -158,14 +191,12 @@ def structure_scores(final, batch, groups=None, novelty_tm=0.5, novelty_ident=0.
     lab = labels.to(dev)
     glab, gsam = torch.unique(lab, sorted=True, return_inverse=True)
     G = glab.numel()
-    nsam = torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gsam, torch.ones(B, dtype=torch.float64, device=dev))
-    novelty = torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gsam, novel.double()) / nsam
+    novelty = _group_sum(novel, gsam, G) / _group_sum(torch.ones_like(gsam), gsam, G)
 
     pairs, gidx, _ = group_pairs(labels)
     gidx = gidx.to(dev)
     ptm = score(final["trans"], final["trans"], pairs)
-    npair = torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, torch.ones_like(gidx, dtype=torch.float64))
-    div_tm = 1.0 - torch.zeros(G, dtype=torch.float64, device=dev).index_add_(0, gidx, ptm.double()) / npair
+    div_tm = 1.0 - _group_sum(ptm, gidx, G) / _group_sum(torch.ones_like(gidx), gidx, G)
     return {"tm": tm, "tm_pooled": tm.double().mean(), "novel": novel, "novelty": novelty, "diversity_tm": div_tm,
             "group_labels": glab}
 
@@ -184,8 +215,7 @@ def secondary_structure(final, batch, backbone="full_atom"):
     generated residues whose simplified codes agree (NaN for a sample without any); ssr_pooled the mean of ssr over the samples
     that have generated residues (float64 scalar); helix, strand, coil [B] the fractions of the sample's generated residues with
     simplified code H, E, C."""
-    if backbone not in ("full_atom", "frames"):
-        raise ValueError(f"backbone must be 'full_atom' or 'frames', got {backbone!r}")
+    _check_backbone(backbone)
     dev = _device(batch["generate_mask"], final["trans"], batch["pos_heavyatom"])
     gen = batch["generate_mask"].to(dev).bool() & batch["res_mask"].to(dev).bool()
     chain = batch["chain_nb"].to(dev) if "chain_nb" in batch else None
@@ -238,28 +268,14 @@ def structural_violations(final, batch, backbone="full_atom", scope="generated")
     have generated residues (float64 scalar); n_clashing_atoms [B] clashing atoms of generated residues.  The same keys with
     `_native` appended for the native complex.  Arrays of the sample (and `*_native`): residue_bond_violation, residue_ca_ca_break,
     residue_clash [B,L] bool, atom_clash, atom_clash_receptor [B,L,14] bool, atom_clash_loss [B,L,14]; residue_index [B,L]."""
-    if backbone not in ("full_atom", "frames"):
-        raise ValueError(f"backbone must be 'full_atom' or 'frames', got {backbone!r}")
     if scope not in ("generated", "all"):
         raise ValueError(f"scope must be 'generated' or 'all', got {scope!r}")
-    dev = _device(batch["generate_mask"], final["trans"], batch["pos_heavyatom"])
-    res_mask = batch["res_mask"].to(dev).bool()
-    gen = batch["generate_mask"].to(dev).bool() & res_mask
-    rotmats, trans, seqs = (final[k].to(dev) for k in ("rotmats", "trans", "seqs"))
-    pos_n, mask_n = batch["pos_heavyatom"].to(dev), batch["mask_heavyatom"].to(dev).bool()
-    chain_nb, res_nb = batch["chain_nb"].to(dev), batch["res_nb"].to(dev)
-    if backbone == "full_atom":
-        pos_s, mask_s = full_atom.reconstruct_sample(rotmats, trans, final["angles"].to(dev), seqs, gen, pos_n)
-        mask_s = torch.where(gen[:, :, None], mask_s, mask_n[:, :, :15])
-    else:
-        pos_s, mask_s = full_atom.reconstruct_sample_bb(rotmats, trans, seqs, chain_nb, res_nb, res_mask, gen, pos_n, mask_n)
-    index = residue_index(chain_nb, res_nb, res_mask)
+    _, res_mask, gen, index, sample, native = _complexes(final, batch, backbone, index=True)
     query = gen if scope == "generated" else None
-    aa_s = torch.where(gen, seqs, final["seqs_1"].to(dev))
     n = gen.sum(1).double()
     has = n > 0
     out = {"residue_index": index}
-    for tag, pos, mask, aa in (("", pos_s, mask_s, aa_s), ("_native", pos_n, mask_n, final["seqs_1"].to(dev))):
+    for tag, (pos, mask, aa) in (("", sample), ("_native", native)):
         v = geometry.structural_violations(pos, mask & res_mask[:, :, None], aa, index, query=query, group=gen)
         bond, brk = v["connection_violation"], v["ca_ca_break"]
         brk = brk | torch.nn.functional.pad(brk[:, :-1], (1, 0))           # a break counts for both of its residues
@@ -277,9 +293,6 @@ def structural_violations(final, batch, backbone="full_atom", scope="generated")
                "atom_clash_receptor": v["clash_atom_cross"], "atom_clash_loss": v["clash_atom_loss"]}
         out.update({k + tag: t for k, t in res.items()})
     return out
-
-
-_APOLAR = {}
 
 
 def apolar_table():
@@ -311,37 +324,21 @@ def interface_area(final, batch, backbone="full_atom", probe_radius=1.4, n_point
       interface_recovery   |S_sample & S_native| / (|S_native| + 1e-10) over the receptor's interface residues.
     Per residue [B,L]: residue_buried (float64), interface_residue (bool).  Every key also with `_native` appended (the native's
     interface_recovery is that of the native against itself).  Relative accessibility is not computed."""
-    if backbone not in ("full_atom", "frames"):
-        raise ValueError(f"backbone must be 'full_atom' or 'frames', got {backbone!r}")
     geometry.sphere_points(n_points)                # checks n_points
     if not float(probe_radius) >= 0.0 or not float(min_buried) >= 0.0:
         raise ValueError(f"probe_radius and min_buried must be >= 0, got {probe_radius}, {min_buried}")
-    dev = _device(batch["generate_mask"], final["trans"], batch["pos_heavyatom"])
-    res_mask = batch["res_mask"].to(dev).bool()
-    gen = batch["generate_mask"].to(dev).bool() & res_mask
+    dev, res_mask, gen, _, sample, native = _complexes(final, batch, backbone)
     rec = res_mask & ~gen
-    rotmats, trans, seqs = (final[k].to(dev) for k in ("rotmats", "trans", "seqs"))
-    pos_n, mask_n = batch["pos_heavyatom"].to(dev), batch["mask_heavyatom"].to(dev).bool()
-    if backbone == "full_atom":
-        pos_s, mask_s = full_atom.reconstruct_sample(rotmats, trans, final["angles"].to(dev), seqs, gen, pos_n)
-        mask_s = torch.where(gen[:, :, None], mask_s, mask_n[:, :, :15])
-    else:
-        pos_s, mask_s = full_atom.reconstruct_sample_bb(rotmats, trans, seqs, batch["chain_nb"].to(dev), batch["res_nb"].to(dev),
-                                                        res_mask, gen, pos_n, mask_n)
-    seqs_1 = final["seqs_1"].to(dev)
-    aa_s = torch.where(gen, seqs, seqs_1)
-    key = str(dev)
-    if key not in _APOLAR:
-        _APOLAR[key] = apolar_table().to(dev)
+    apolar_tab = geometry._table("apolar", dev, apolar_table)
     has = gen.any(1)
     nan = torch.full((gen.shape[0],), float("nan"), dtype=torch.float64, device=dev)
     out, site = {}, {}
-    for tag, pos, mask, aa in (("", pos_s, mask_s, aa_s), ("_native", pos_n, mask_n, seqs_1)):
+    for tag, (pos, mask, aa) in (("", sample), ("_native", native)):
         v = geometry.sasa(pos, mask & res_mask[:, :, None], aa, group=gen, probe_radius=probe_radius, n_points=n_points)
         S = v["sasa_atom"].shape[2]
         buried_atom = v["sasa_atom_own"].double() - v["sasa_atom"].double()
         buried = buried_atom.sum(-1)
-        apolar = _APOLAR[key][torch.where((aa < 0) | (aa > 19), 20, aa)][:, :, :S]
+        apolar = apolar_tab[torch.where((aa < 0) | (aa > 19), 20, aa)][:, :, :S]
         over = lambda x, m: (x * m).sum(1)  # noqa: E731
         free, bound = over(v["sasa_atom_own"].double().sum(-1), gen), over(v["sasa_atom"].double().sum(-1), gen)
         b_pep, b_rec = over(buried, gen), over(buried, rec)
@@ -384,19 +381,11 @@ def sidechain_packing(final, batch, correct_tol_deg=20.0):
     tol = float(correct_tol_deg)
     if not 0.0 <= tol <= 180.0:
         raise ValueError(f"correct_tol_deg must be in [0, 180], got {correct_tol_deg}")
-    dev = _device(batch["generate_mask"], final["trans"], batch["pos_heavyatom"])
-    res_mask = batch["res_mask"].to(dev).bool()
-    gen = batch["generate_mask"].to(dev).bool() & res_mask
-    rotmats, trans, seqs = (final[k].to(dev) for k in ("rotmats", "trans", "seqs"))
-    seqs_1 = final["seqs_1"].to(dev)
-    pos_n, mask_n = batch["pos_heavyatom"].to(dev), batch["mask_heavyatom"].to(dev).bool()
-    pos_s, mask_s = full_atom.reconstruct_sample(rotmats, trans, final["angles"].to(dev), seqs, gen, pos_n)
-    mask_s = torch.where(gen[:, :, None], mask_s, mask_n[:, :, :15])
-    aa_s = torch.where(gen, seqs, seqs_1)
-    index = residue_index(batch["chain_nb"].to(dev), batch["res_nb"].to(dev), res_mask)
+    dev, res_mask, gen, index, sample, native = _complexes(final, batch, "full_atom", index=True)
+    seqs_1 = native[2]
     B, L = gen.shape
     sides = []
-    for pos, mask, aa in ((pos_s, mask_s, aa_s), (pos_n, mask_n, seqs_1)):
+    for pos, mask, aa in (sample, native):
         t = geometry.torsion_angles(pos, mask & res_mask[:, :, None], aa, index)
         sides.append(dict(pos=pos, atom_mask=mask & gen[:, :, None], aa=aa, angles=t["angles"], defined=t["defined"] & gen[:, :, None]))
     ids = torch.arange(B, dtype=torch.int32, device=dev)
@@ -411,8 +400,8 @@ def sidechain_packing(final, batch, correct_tol_deg=20.0):
     chi_err = c["err"][:, :, 4:] * deg
     compared = ~torch.isnan(chi_err)
     types = seqs_1.clamp(0, 19).reshape(-1)
-    by_sum = torch.zeros(20, 4, dtype=torch.float64, device=dev).index_add_(0, types, torch.nan_to_num(chi_err).double().reshape(-1, 4))
-    by_n = torch.zeros(20, 4, dtype=torch.int64, device=dev).index_add_(0, types, compared.reshape(-1, 4).long())
+    by_sum = _group_sum(torch.nan_to_num(chi_err).reshape(-1, 4), types, 20)
+    by_n = _group_sum(compared.reshape(-1, 4), types, 20, dtype=torch.int64)
     sc_n = c["sc_n"].double()
     return {"chi_mae": mae[:, 4:], "chi_correct": share[:, 4:], "residue_correct": c["res_correct"].double() / c["res_with_chi"].double(),
             "psi_o_mae": mae[:, 3], "phi_mae": mae[:, 1], "psi_mae": mae[:, 2], "sc_rmsd": c["sc_rmsd"], "n_chi": c["err_count"][:, 4:],

@@ -9,7 +9,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
 import eval_oracle as EO  # noqa: E402
-from pepflowww_amd import geometry, metrics, synth  # noqa: E402
+from pepflowww_amd import _capi, geometry, metrics, synth  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -70,3 +70,30 @@ def test_one_group_needs_equal_generate_masks():
         metrics.evaluate_samples(final, batch, groups=torch.tensor([0, 0, 1]))
     with pytest.raises(ValueError):
         metrics.evaluate_samples(final, batch, groups=torch.tensor([0, 1]))
+
+
+def test_superpose_rejects_bad_arguments_before_device_work():
+    """the cases tm_score has in test_tm_cpu.py: superpose goes through the same pair-work-list checks"""
+    x = torch.zeros(4, 10, 3)
+    m = torch.ones(4, 10, dtype=torch.bool)
+    aa = torch.zeros(4, 10, dtype=torch.long)
+    pairs = torch.tensor([[0, 1]], dtype=torch.int32)
+    with pytest.raises(ValueError):
+        geometry.superpose(torch.zeros(4, 10), x, m, m, pairs)                         # a 2-D x
+    with pytest.raises(ValueError):
+        geometry.superpose(x, torch.zeros(4, 9, 3), m, m, pairs)                       # y of another N
+    with pytest.raises(ValueError):
+        geometry.superpose(x, torch.zeros(4, 10), m, m, pairs)                         # a 2-D y
+    with pytest.raises(ValueError):
+        geometry.superpose(x, x, m[:, :9], m, pairs)                                   # mx
+    with pytest.raises(ValueError):
+        geometry.superpose(x, x, m, m[:3], pairs)                                      # my
+    for bad in (torch.zeros(3, dtype=torch.int32), torch.zeros(2, 3, dtype=torch.int32), torch.zeros(4, dtype=torch.int32)):
+        with pytest.raises(ValueError):
+            geometry.superpose(x, x, m, m, bad)                                        # pairs that is not [P,2]
+    with pytest.raises(ValueError):
+        geometry.superpose(x, x, m, m, pairs, aa_x=aa)                                 # exactly one of aa_x / aa_y
+    with pytest.raises(ValueError):
+        geometry.superpose(x, x, m, m, pairs, aa_y=aa)
+    with pytest.raises(_capi.PepflowHipError):                                         # valid shapes on the CPU: no fallback
+        geometry.superpose(x, x, m, m, pairs)
