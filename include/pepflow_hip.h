@@ -1050,6 +1050,66 @@ typedef struct {
 } pf_sidechain_compare_args;
 int pf_sidechain_compare_fwd(const pf_sidechain_compare_args* a, pf_stream_t stream);
 
+/* ---- lDDT and interface contacts (ABI 64, added entry points) ------------------------------------------------------------------
+ * Both take the work-list family of pf_sidechain_compare_fwd: pair p = (i, j) of pairs [P,2] looks at the model x[i] and the reference
+ * structure y[j] (y may alias x); group / query [By,N] belong to y; a pair with an index out of range gives zeros (min_dist: +inf).
+ * One launch each (per 65535 pairs), no atomics, no scratch, nothing pair-sized; integer outputs, flags and minima with one writer:
+ * bit-identical from run to run, independent of the rest of the batch and of the order of the list.  N > 512 -> PF_E_TOOLARGE.
+ *
+ * pf_lddt_fwd: the counts of the local distance difference test with the values of OpenFold's `lddt` / `lddt_ca`
+ * (openfold/utils/loss.py:382-458); the conventions are listed in csrc/lddt.hip.  Slots 0..13 are read.  An atom is compared when its
+ * slot is in slot_mask (0x2: CA, 0xF: N CA C O, 0x3FFF: all), it is set in mask_x[i] and mask_y[j] and, for slots >= 4,
+ * aa_x == aa_y at the residue.  A pair of compared atoms is scored when d_y = sqrt(1e-10 + |a - b|^2) < cutoff in y, they are not the
+ * same atom and, with exclude_same_residue, not of one residue (0: the reference's behaviour); it adds
+ * [|d_y - d_x| < 0.5] + [< 1] + [< 2] + [< 4] to kept.
+ *   scored, kept [P,N]                     per row residue, summed over its atoms;
+ *   scored_cross, kept_cross [P,N]         partners whose residue has another group byte (optional, both or neither; need group);
+ *   scored_atom, kept_atom [P,N,14]        per row atom (optional, both or neither);
+ *   scored_atom_cross, kept_atom_cross     (optional, both or neither; need group).
+ * With query only rows in query residues are evaluated (the rest 0); every compared atom is still a partner.
+ *
+ * pf_contacts_fwd: residue contacts across the groups, in x[i] and in y[j] at once (DockQ's Fnat and interface, Basu & Wallner 2016);
+ * the conventions are listed in csrc/contacts.hip.  Slots 0 .. min(n_atoms, 15) - 1 in slot_mask are read, each structure on its own
+ * atom_mask.  A residue pair (p, q) counts when the group bytes differ and each residue has an atom in x[i] and one in y[j]; m_x, m_y:
+ * its minimal squared atom distance in each structure (fp32), compared as m < cutoff^2.
+ *   contacts_x, contacts_y, contacts_shared [P,N]   the q in contact (contact_cutoff) in x, in y, in both;
+ *   interface_x, interface_y [P,N]                  1 where some q is within interface_cutoff;
+ *   min_dist_x, min_dist_y [P,N]                    sqrt of the smallest m over the counted q, +inf without any. */
+#define PF_LDDT_MAX_N 512
+#define PF_LDDT_SLOTS 14
+#define PF_CONTACTS_MAX_N 512
+#define PF_CONTACTS_SLOTS 15
+typedef struct {
+    const float* pos_x; const float* pos_y;                         /* [Bx,N,n_atoms_x,3], [By,N,n_atoms_y,3] */
+    const unsigned char* mask_x; const unsigned char* mask_y;       /* [Bx,N,n_atoms_x], [By,N,n_atoms_y] */
+    const int64_t* aa_x; const int64_t* aa_y;                       /* [Bx,N], [By,N] */
+    const int* pairs;                                               /* [P,2] */
+    const unsigned char* group;                                     /* [By,N] optional */
+    const unsigned char* query;                                     /* [By,N] optional */
+    int* scored; int* kept;                                         /* [P,N] */
+    int* scored_cross; int* kept_cross;                             /* [P,N] optional */
+    int* scored_atom; int* kept_atom;                               /* [P,N,14] optional */
+    int* scored_atom_cross; int* kept_atom_cross;                   /* [P,N,14] optional */
+    int Bx, By, N, P, n_atoms_x, n_atoms_y;
+    int slot_mask, exclude_same_residue;
+    float cutoff;                                                   /* > 0; 15.0 */
+} pf_lddt_args;
+int pf_lddt_fwd(const pf_lddt_args* a, pf_stream_t stream);
+
+typedef struct {
+    const float* pos_x; const float* pos_y;                         /* [Bx,N,n_atoms_x,3], [By,N,n_atoms_y,3] */
+    const unsigned char* mask_x; const unsigned char* mask_y;       /* [Bx,N,n_atoms_x], [By,N,n_atoms_y] */
+    const int* pairs;                                               /* [P,2] */
+    const unsigned char* group;                                     /* [By,N] */
+    int* contacts_x; int* contacts_y; int* contacts_shared;         /* [P,N] */
+    unsigned char* interface_x; unsigned char* interface_y;         /* [P,N] */
+    float* min_dist_x; float* min_dist_y;                           /* [P,N] */
+    int Bx, By, N, P, n_atoms_x, n_atoms_y;
+    int slot_mask;
+    float contact_cutoff, interface_cutoff;                         /* > 0; 5.0, 10.0 */
+} pf_contacts_args;
+int pf_contacts_fwd(const pf_contacts_args* a, pf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

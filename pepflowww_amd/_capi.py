@@ -224,6 +224,21 @@ class SidechainCompareArgs(C.Structure):
                 ("Bx", _i), ("By", _i), ("N", _i), ("P", _i), ("n_atoms_x", _i), ("n_atoms_y", _i), ("correct_tol", C.c_float)]
 
 
+class LddtArgs(C.Structure):
+    _fields_ = [("pos_x", _fp), ("pos_y", _fp), ("mask_x", _fp), ("mask_y", _fp), ("aa_x", _fp), ("aa_y", _fp), ("pairs", _fp),
+                ("group", _fp), ("query", _fp), ("scored", _fp), ("kept", _fp), ("scored_cross", _fp), ("kept_cross", _fp),
+                ("scored_atom", _fp), ("kept_atom", _fp), ("scored_atom_cross", _fp), ("kept_atom_cross", _fp),
+                ("Bx", _i), ("By", _i), ("N", _i), ("P", _i), ("n_atoms_x", _i), ("n_atoms_y", _i), ("slot_mask", _i),
+                ("exclude_same_residue", _i), ("cutoff", C.c_float)]
+
+
+class ContactsArgs(C.Structure):
+    _fields_ = [("pos_x", _fp), ("pos_y", _fp), ("mask_x", _fp), ("mask_y", _fp), ("pairs", _fp), ("group", _fp),
+                ("contacts_x", _fp), ("contacts_y", _fp), ("contacts_shared", _fp), ("interface_x", _fp), ("interface_y", _fp),
+                ("min_dist_x", _fp), ("min_dist_y", _fp), ("Bx", _i), ("By", _i), ("N", _i), ("P", _i), ("n_atoms_x", _i),
+                ("n_atoms_y", _i), ("slot_mask", _i), ("contact_cutoff", C.c_float), ("interface_cutoff", C.c_float)]
+
+
 class EtBwdArgs(C.Structure):
     _fields_ = [("g_y", _fp), ("h1", _fp), ("h2", _fp), ("wfT_f16", _fp), ("w2T_f16", _fp), ("w1T_f16", _fp),
                 ("g_h2", _fp), ("g_h1", _fp), ("g_x", _fp), ("npairs", C.c_longlong), ("m1", _fp), ("m2", _fp)]
@@ -308,6 +323,8 @@ _SIGNATURES = {
     "pf_sasa_fwd": ([C.POINTER(SasaArgs), _fp], _i),
     "pf_torsions_fwd": ([C.POINTER(TorsionsArgs), _fp], _i),
     "pf_sidechain_compare_fwd": ([C.POINTER(SidechainCompareArgs), _fp], _i),
+    "pf_lddt_fwd": ([C.POINTER(LddtArgs), _fp], _i),
+    "pf_contacts_fwd": ([C.POINTER(ContactsArgs), _fp], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -1,11 +1,14 @@
 """Evaluation geometry on the device: thin wrappers that check their arguments, bind device pointers into one argument struct and
-launch one HIP entry point each (the kernels and their conventions are described in csrc/*.hip; DESIGN.md 3.8-3.14).
+launch one HIP entry point each (the kernels and their conventions are described in csrc/*.hip; DESIGN.md 3.8-3.15).
 
-Two input families, one binding path each:
+Input families, one binding path each:
   pair work lists   point sets x [Bx,N,3] / y [By,N,3] with masks and `pairs` [P,2] -- `_pair_inputs`: superpose (and align, batch_align,
                     superpose_rmsd), tm_score, tm_align and their pairwise_* matrices (`_within_groups`, `_mirrored`);
   heavy-atom structures   pos [B,N,A,3], atom_mask [B,N,A] and per-residue [B,N] tensors -- `_structure`: structural_violations, sasa,
-                    torsion_angles and each side of sidechain_compare (dssp reads the same pos with a residue mask).
+                    torsion_angles and each side of sidechain_compare (dssp reads the same pos with a residue mask);
+  both at once      two heavy-atom structure sets and a work list -- `_structure_pairs`: lddt (pf_lddt_fwd, the values of OpenFold's
+                    lddt / lddt_ca, openfold/utils/loss.py:382-458) and interface_contacts (pf_contacts_fwd), which dockq combines
+                    with `superpose` into Fnat, iRMSD, LRMSD and DockQ.
 `_bind_in` / `_bind_out` fill the struct, `_as_bool` turns the byte outputs into bool, `_table` keeps the per-device constant tables.
 
 Deviation from the reference: `batch_align` selects each sample's masked atoms on their own.  The reference's
@@ -604,3 +607,165 @@ def sidechain_compare(x, y, pairs, correct_tol=math.radians(20), per_residue=Fal
         _capi.check(_capi.load().pf_sidechain_compare_fwd(C.byref(a), _capi.stream_ptr()), "pf_sidechain_compare_fwd")
     _as_bool(out, "swapped")
     return out
+
+
+LDDT_MAX_N = 512            # PF_LDDT_MAX_N / PF_CONTACTS_MAX_N: the most residues pf_lddt_fwd and pf_contacts_fwd take
+LDDT_SLOTS = 14             # PF_LDDT_SLOTS: the per-atom outputs of pf_lddt_fwd
+SLOT_MASKS = {"ca": 0x2, "backbone": 0xF, "all": 0x3FFF}       # bit s: heavy-atom slot s (N, CA, C, O, then the side chain)
+
+
+def _slot_mask(slots):
+    if isinstance(slots, str) and slots in SLOT_MASKS:
+        return SLOT_MASKS[slots]
+    if isinstance(slots, int) and not isinstance(slots, bool) and 0 < slots < 1 << 15:
+        return slots
+    raise ValueError(f"slots must be one of {tuple(SLOT_MASKS)} or a bit mask of the slots 0..14, got {slots!r}")
+
+
+def _positive(name, v):
+    v = float(v)
+    if not 0.0 < v < 1e6:
+        raise ValueError(f"{name} must be a positive length in A, got {v}")
+    return v
+
+
+def _structure_pairs(a, name, x, y, pairs, group, query=None, with_aa=True):
+    """The inputs of pf_lddt_fwd / pf_contacts_fwd: x, y dicts with pos [B.,N,A.,3], atom_mask [B.,N,A.], aa [B.,N] (y may be x), the
+    work list pairs [P,2], group / query [By,N] (they belong to y); N <= LDDT_MAX_N.  Checks (ValueError), converts through
+    `_structure` and binds everything into `a`.  -> (the tensors to keep alive, device, N, P)"""
+    for nm, d in (("x", x), ("y", y)):
+        if not isinstance(d, dict) or any(k not in d for k in _COMPARE_KEYS[:3]):
+            raise ValueError(f"{nm} must be a dict with {_COMPARE_KEYS[:3]}")
+    pairs = _check_pairs(pairs)
+    dev = x["pos"].device if isinstance(x["pos"], torch.Tensor) else None
+
+    def side(d, nm, extra=()):
+        _, (B, N, A), pos, atom_mask, conv = _structure(d["pos"], d["atom_mask"], (("aa", d["aa"], torch.int64),) + extra,
+                                                        max_n=LDDT_MAX_N, tag=nm + ".", dev=dev)
+        return (B, N, A), [pos, atom_mask] + conv
+    per_y = (("group", group, torch.uint8), ("query", query, torch.uint8))
+    (By, Ny, Ay), ky = side(y, "y", per_y)
+    (Bx, N, Ax), kx = ((By, Ny, Ay), ky) if y is x else side(x, "x")
+    if Ny != N:
+        raise ValueError(f"x and y must have the same number of residues, got {N} and {Ny}")
+    if N == 0 or Bx == 0 or By == 0:
+        raise ValueError(f"{name} needs at least one structure of at least one residue on each side")
+    keep = kx[:3] + ky + [pairs.to(dev, torch.int32).contiguous()]
+    _bind_in(a, pos_x=kx[0], mask_x=kx[1], pos_y=ky[0], mask_y=ky[1], group=ky[3], query=ky[4], pairs=keep[-1],
+             **(dict(aa_x=kx[2], aa_y=ky[2]) if with_aa else {}))
+    a.Bx, a.By, a.N, a.P, a.n_atoms_x, a.n_atoms_y = Bx, By, N, pairs.shape[0], Ax, Ay
+    return keep, dev, N, pairs.shape[0]
+
+
+def lddt(x, y, pairs, slots="all", cutoff=15.0, exclude_same_residue=False, group=None, query=None, per_atom=False):
+    """pf_lddt_fwd over the work list `pairs` [P,2] (pair p = (i, j): the model x[i] against the reference structure y[j]): the local
+    distance difference test with the values of OpenFold's `lddt` / `lddt_ca` (openfold/utils/loss.py:382-458; conventions:
+    csrc/lddt.hip).  No superposition is involved.
+
+    x, y: dicts with pos [B.,N,A.,3], atom_mask [B.,N,A.], aa [B.,N] as `sidechain_compare` takes them (y may be x); N <= 512.
+    slots: "ca", "backbone" (N, CA, C, O), "all" (the 14 heavy-atom slots) or a bit mask of slots; an atom is compared where both masks
+    have it and, for side-chain slots, the residue types agree.  A pair of compared atoms is scored when it is closer than `cutoff` in
+    y; exclude_same_residue=False scores pairs inside a residue too, as the reference does (True: Mariani et al.'s lDDT).  group
+    [By,N] (optional): adds the *_cross outputs, over partners of another group byte; query [By,N] (optional): only rows in query
+    residues are evaluated, every compared atom is still a partner.
+    -> dict of device tensors: scored, kept [P,N] int32 (per row residue: scored pairs, and the thresholds 0.5 / 1 / 2 / 4 A they
+    keep); lddt_residue [P,N] = kept / (4 scored), lddt [P] from the counts summed over the rows, float64; with `group`
+    scored_cross, kept_cross, lddt_residue_cross, lddt_cross; with `per_atom` scored_atom, kept_atom [P,N,14] (and *_atom_cross).
+    Deviation from the reference: its (eps + sum) / (eps + n) gives 1.0 for a row without a scored pair; here such a row is NaN."""
+    slot_mask, cutoff = _slot_mask(slots) & 0x3FFF, _positive("cutoff", cutoff)
+    a = _capi.LddtArgs()
+    keep, dev, N, P = _structure_pairs(a, "lddt", x, y, pairs, group, query)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = {"scored": i32(P, N), "kept": i32(P, N)}
+    tags = ("", "_cross") if group is not None else ("",)
+    if group is not None:
+        out.update(scored_cross=i32(P, N), kept_cross=i32(P, N))
+    if per_atom:
+        for t in tags:
+            out.update({"scored_atom" + t: i32(P, N, LDDT_SLOTS), "kept_atom" + t: i32(P, N, LDDT_SLOTS)})
+    _bind_out(a, out)
+    a.slot_mask, a.exclude_same_residue, a.cutoff = slot_mask, int(bool(exclude_same_residue)), cutoff
+    if P:
+        _capi.check(_capi.load().pf_lddt_fwd(C.byref(a), _capi.stream_ptr()), "pf_lddt_fwd")
+    for t in tags:
+        s, k = out["scored" + t].double(), out["kept" + t].double()
+        out["lddt_residue" + t] = k / (4.0 * s)                 # 0 / 0: NaN where nothing is scored
+        out["lddt" + t] = k.sum(1) / (4.0 * s.sum(1))
+    return out
+
+
+def interface_contacts(x, y, pairs, group, slots="all", contact_cutoff=5.0, interface_cutoff=10.0):
+    """pf_contacts_fwd over the work list `pairs` [P,2]: the residue contacts between the groups in the model x[i] and in the reference
+    structure y[j] at once (conventions: csrc/contacts.hip).  x, y as in `lddt`; group [By,N] (required) belongs to y.  A residue pair
+    counts when its group bytes differ and both residues have an atom in both structures -- each structure on its own atom_mask, no
+    residue-type rule; its distance is the smallest one between their atoms (slots: as in `lddt`; a mask may name slot 14, OXT).
+    -> dict of device tensors, per row residue [P,N]: contacts_x, contacts_y, contacts_shared int32 (the partners within
+    contact_cutoff in x, in y, in both); interface_x, interface_y bool (a partner within interface_cutoff); min_dist_x, min_dist_y
+    float32 (the nearest atom of a counted partner, +inf without any).  Each residue pair shows in both of its rows."""
+    if group is None:
+        raise ValueError("interface_contacts needs `group` [By,N]: the contacts are those between residues of different groups")
+    slot_mask = _slot_mask(slots)
+    contact_cutoff, interface_cutoff = _positive("contact_cutoff", contact_cutoff), _positive("interface_cutoff", interface_cutoff)
+    a = _capi.ContactsArgs()
+    keep, dev, N, P = _structure_pairs(a, "interface_contacts", x, y, pairs, group, with_aa=False)
+    out = {k: torch.empty(P, N, dtype=torch.int32, device=dev) for k in ("contacts_x", "contacts_y", "contacts_shared")}
+    out.update({k: torch.empty(P, N, dtype=torch.uint8, device=dev) for k in ("interface_x", "interface_y")})
+    out.update({k: torch.empty(P, N, device=dev) for k in ("min_dist_x", "min_dist_y")})
+    _bind_out(a, out)
+    a.slot_mask, a.contact_cutoff, a.interface_cutoff = slot_mask, contact_cutoff, interface_cutoff
+    if P:
+        _capi.check(_capi.load().pf_contacts_fwd(C.byref(a), _capi.stream_ptr()), "pf_contacts_fwd")
+    _as_bool(out, "interface_x", "interface_y")
+    return out
+
+
+DOCKQ_CLASSES = ("incorrect", "acceptable", "medium", "high")       # dockq_class 0..3: DockQ < 0.23, < 0.49, < 0.80, >= 0.80
+
+
+def dockq_score(fnat, irmsd, lrmsd):
+    """DockQ = (Fnat + 1 / (1 + (iRMSD / 1.5)^2) + 1 / (1 + (LRMSD / 8.5)^2)) / 3 (Basu & Wallner, PLoS ONE 2016, eq. 1-2)"""
+    return (fnat + 1.0 / (1.0 + (irmsd / 1.5) ** 2) + 1.0 / (1.0 + (lrmsd / 8.5) ** 2)) / 3.0
+
+
+def dockq(x, y, pairs, group, contact_cutoff=5.0, interface_cutoff=10.0):
+    """DockQ of the model x[i] against the native y[j] for every pair of `pairs` [P,2], written from the publication (Basu & Wallner,
+    PLoS ONE 2016); it has not been checked against the DockQ program.  x, y as in `lddt`; group [By,N] belongs to y, != 0 marks the
+    ligand (the peptide), 0 the receptor.  The CAPRI-peptide cut-offs are contact_cutoff=4.0, interface_cutoff=8.0.
+    -> dict of device tensors, per pair [P], float64:
+      fnat      the native's residue contacts (heavy atoms within contact_cutoff across the groups) that the model has: sum over the
+                ligand of contacts_shared / contacts_y (NaN without native contacts);
+      fnonnat   the model's contacts that the native lacks, over the model's (NaN without any);
+      irmsd     `superpose`'s rmsd over N, CA, C, O of the native's interface residues (a partner within interface_cutoff in y; both
+                sides of the interface) where both structures have the atom;
+      lrmsd     the ligand's N, CA, C, O rmsd_plain after superposing the receptor's N, CA, C, O;
+      dockq     `dockq_score`; dockq_class int64 0..3 (DOCKQ_CLASSES; 0 where dockq is NaN);
+    n_native_contacts, n_sample_contacts, n_shared_contacts [P] int64 (summed over the ligand), n_interface [P] int64, and the
+    outputs of `interface_contacts`.  A pair with an index out of range is NaN."""
+    c = interface_contacts(x, y, pairs, group, "all", contact_cutoff, interface_cutoff)
+    dev = c["contacts_x"].device
+    pairs = _check_pairs(pairs).to(dev, torch.int64)
+    Bx, N = x["pos"].shape[:2]
+    By = y["pos"].shape[0]
+    ok = (pairs[:, 0] >= 0) & (pairs[:, 0] < Bx) & (pairs[:, 1] >= 0) & (pairs[:, 1] < By)
+    i, j = pairs[:, 0].clamp(0, Bx - 1), pairs[:, 1].clamp(0, By - 1)
+    lig = (torch.as_tensor(group).to(dev) != 0)[j] & ok[:, None]                       # [P,N]
+    over = lambda t: (t.to(torch.int64) * lig).sum(1)  # noqa: E731
+    n_y, n_x, n_s = over(c["contacts_y"]), over(c["contacts_x"]), over(c["contacts_shared"])
+    fnat = n_s.double() / n_y.double()
+    fnonnat = (n_x - n_s).double() / n_x.double()
+    # the backbone atoms of each pair as one point set [P, 4 N, 3]; three masks on it
+    P = pairs.shape[0]
+    bx, by = _f32(x["pos"].to(dev)[i][:, :, :4], dev).reshape(P, 4 * N, 3), _f32(y["pos"].to(dev)[j][:, :, :4], dev).reshape(P, 4 * N, 3)
+    both = (x["atom_mask"].to(dev)[i][:, :, :4] != 0) & (y["atom_mask"].to(dev)[j][:, :, :4] != 0) & ok[:, None, None]
+    on = lambda m: (both & m[:, :, None]).reshape(P, 4 * N)  # noqa: E731
+    diag = torch.arange(P, dtype=torch.int32, device=dev)[:, None].expand(P, 2)
+    face, rec = on(c["interface_y"]), on(~lig & ok[:, None])
+    irmsd = superpose(bx, by, face, face, diag)["rmsd"].double()
+    placed = superpose(bx, by, rec, rec, diag, aligned=True)["aligned"]
+    lrmsd = superpose(placed, by, on(lig), on(lig), diag)["rmsd_plain"].double()
+    score = dockq_score(fnat, irmsd, lrmsd)
+    cls = (score >= 0.23).long() + (score >= 0.49).long() + (score >= 0.80).long()
+    res = {"fnat": fnat, "fnonnat": fnonnat, "irmsd": irmsd, "lrmsd": lrmsd, "dockq": score, "dockq_class": cls,
+           "n_native_contacts": n_y, "n_sample_contacts": n_x, "n_shared_contacts": n_s, "n_interface": c["interface_y"].sum(1)}
+    res.update(c)
+    return res

@@ -6,10 +6,12 @@ and TM-score diversity (`structure_scores`); DSSP secondary structure and the se
 79-91 (`secondary_structure`); clashes and broken peptide bonds, AlphaFold's between-residue structural violations
 (`structural_violations`); solvent-accessible surface and the area buried between peptide and receptor (`interface_area`); the
 side-chain packing table, chi1-chi4 errors against the native and the share of residues with every chi within a tolerance
-(`sidechain_packing`).
+(`sidechain_packing`); superposition-free local accuracy, lDDT with the values of OpenFold's lddt / lddt_ca
+(openfold/utils/loss.py:382-458), over the peptide and across the interface (`local_accuracy`); docking quality, Fnat, iRMSD, LRMSD and
+DockQ (`docking_quality`).
 
 Every per-residue, per-point and per-atom-pair operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd /
-pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
+pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
@@ -412,3 +414,59 @@ def sidechain_packing(final, batch, correct_tol_deg=20.0):
             "chi_mae_by_type": by_sum / by_n.double(), "n_chi_by_type": by_n,
             "chi_err": chi_err, "residue_sc_rmsd": torch.sqrt(c["sc_sq"].double() / sc_n).float(), "swapped": c["swapped"],
             "angles_sample": sides[0]["angles"], "angles_native": sides[1]["angles"]}
+
+
+def _mean_of_defined(v):
+    """the mean of v [B] over its entries that are not NaN (NaN when there is none), float64"""
+    has = ~torch.isnan(v)
+    return torch.nan_to_num(v.double()).sum() / has.sum().double()
+
+
+def local_accuracy(final, batch, backbone="full_atom", cutoff=15.0):
+    """lDDT of each sample's generated residues against the native complex: a local accuracy that needs no superposition
+    (geometry.lddt, the values of OpenFold's lddt / lddt_ca).  final / batch and the two complexes are those of `structural_violations`:
+    backbone "full_atom" -- generated residues rebuilt with all heavy atoms, the context kept; "frames" -- generated residues as N, CA,
+    C, O only (lddt_all then covers those atoms).  Rows are the generated residues (query = generate_mask & res_mask), every residue of
+    the complex is a partner, group = the same mask.  Atom pairs inside a residue are scored, as the reference scores them.
+
+    -> dict of device tensors.  Per sample [B], float64, NaN for a sample without generated residues (or without a scored pair):
+      lddt_ca, lddt_backbone, lddt_all     over CA; N, CA, C, O; all heavy atoms (side chains where the residue types agree);
+      ilddt_ca, ilddt_backbone, ilddt_all  the same over the pairs across the groups only: does the peptide keep its distances to
+                                           the receptor (this package's name for it);
+    per residue: lddt_residue [B,L] (all atoms, NaN off the generated residues); pooled: lddt_ca_pooled, lddt_backbone_pooled,
+    lddt_all_pooled and the three ilddt_*_pooled, the mean over the samples that have a value (float64 scalars)."""
+    cutoff = float(cutoff)
+    dev, res_mask, gen, _, sample, native = _complexes(final, batch, backbone)
+    x, y = (dict(pos=pos, atom_mask=mask & res_mask[:, :, None], aa=aa) for pos, mask, aa in (sample, native))
+    ids = torch.arange(gen.shape[0], dtype=torch.int32, device=dev)
+    diag = torch.stack([ids, ids], 1)
+    out = {}
+    for name in ("ca", "backbone", "all"):
+        v = geometry.lddt(x, y, diag, slots=name, cutoff=cutoff, group=gen, query=gen)
+        out["lddt_" + name], out["ilddt_" + name] = v["lddt"], v["lddt_cross"]
+        out["lddt_" + name + "_pooled"], out["ilddt_" + name + "_pooled"] = _mean_of_defined(v["lddt"]), _mean_of_defined(v["lddt_cross"])
+    out["lddt_residue"] = v["lddt_residue"]
+    return out
+
+
+def docking_quality(final, batch, backbone="full_atom", contact_cutoff=5.0, interface_cutoff=10.0):
+    """DockQ of each sample's peptide on its receptor against the native complex (geometry.dockq: Basu & Wallner 2016, written from
+    the publication and not checked against the DockQ program).  final / batch and the two complexes are those of
+    `structural_violations`; the ligand is generate_mask & res_mask, the receptor the other residues of res_mask.  With
+    backbone="frames" the sample's generated residues have N, CA, C, O only while the native keeps its side chains, so the sample's
+    contacts -- and with them fnat -- are undercounted; "full_atom" is the default.  The CAPRI-peptide cut-offs are
+    contact_cutoff=4.0, interface_cutoff=8.0.
+
+    -> dict of device tensors.  Per sample [B]: fnat, fnonnat, irmsd, lrmsd, dockq (float64; NaN for a sample without native
+    contacts), dockq_class (int64, 0 incorrect .. 3 high), n_native_contacts, n_sample_contacts (int64, residue pairs).  Pooled, this
+    package's pooling: dockq_pooled, the mean over the samples that have a value, and success_rate, the share of those with DockQ >=
+    0.23 (float64 scalars)."""
+    dev, res_mask, gen, _, sample, native = _complexes(final, batch, backbone)
+    x, y = (dict(pos=pos, atom_mask=mask & res_mask[:, :, None], aa=aa) for pos, mask, aa in (sample, native))
+    ids = torch.arange(gen.shape[0], dtype=torch.int32, device=dev)
+    d = geometry.dockq(x, y, torch.stack([ids, ids], 1), gen, contact_cutoff=contact_cutoff, interface_cutoff=interface_cutoff)
+    out = {k: d[k] for k in ("fnat", "fnonnat", "irmsd", "lrmsd", "dockq", "dockq_class", "n_native_contacts", "n_sample_contacts")}
+    has = ~torch.isnan(d["dockq"])
+    out["dockq_pooled"] = _mean_of_defined(d["dockq"])
+    out["success_rate"] = (has & (d["dockq"] >= 0.23)).sum().double() / has.sum().double()
+    return out
