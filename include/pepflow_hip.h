@@ -1110,6 +1110,40 @@ typedef struct {
 } pf_contacts_args;
 int pf_contacts_fwd(const pf_contacts_args* a, pf_stream_t stream);
 
+/* ---- empirical interface energy (ABI 64, added entry point) -----------------------------------------------------------------------
+ * pf_interface_energy_fwd: the functional form of AutoDock Vina's scoring function (Trott & Olson, J. Comput. Chem. 2010) over the
+ * heavy atoms of a batch of structures, between atoms of residues whose group bytes differ; the conventions are listed in
+ * csrc/interface_energy.hip.  Written from the publication and checked against a float64 restatement; it is not checked against the
+ * Vina program, and it is neither Vina's output nor Rosetta's dG_separated.  Slots 0 .. min(n_atoms, 15) - 1 are read; an atom takes
+ * part where atom_mask is set and radius has an entry for its type and slot.  A pair counts when r < cutoff; d = r - R_i - R_j.
+ *   terms_atom [B,N,15,5]        per row atom, the unweighted sums of gauss1, gauss2, repulsion, hydrophobic, hbond over its partners;
+ *   pairs_atom, hbond_pairs_atom, hydrophobic_pairs_atom [B,N,15]   partners inside the cutoff, with hbond > 0, with hydrophobic > 0;
+ *   terms_residue [B,N,5]        the sum over the slots;  energy_residue [B,N] = sum_k w_k terms_residue[k].
+ * Each pair shows in both of its rows.  With query only atoms of query residues are rows (a participating atom that is not one has
+ * counts -1 and zero terms); every participating atom is still a partner.  work: [B,N,4] floats, no initialisation needed.  Two
+ * launches, no atomics, nothing pair-sized, one writer per output: bit-identical from run to run and independent of the rest of the
+ * batch.  N > PF_INTERFACE_ENERGY_MAX_N or B > 65535 -> PF_E_TOOLARGE. */
+#define PF_INTERFACE_ENERGY_MAX_N 512
+#define PF_INTERFACE_ENERGY_SLOTS 15
+typedef struct {
+    const float* pos;                                               /* [B,N,n_atoms,3] */
+    const unsigned char* atom_mask;                                 /* [B,N,n_atoms] */
+    const int64_t* aa;                                              /* [B,N] */
+    const unsigned char* group;                                     /* [B,N] */
+    const unsigned char* query;                                     /* [B,N] optional */
+    const float* radius;                                            /* [21,15] XS radii, 0: the type has no such atom */
+    const unsigned char* types;                                     /* [21,15] bit 0 hydrophobic, bit 1 donor, bit 2 acceptor */
+    float* work;                                                    /* [B,N,4] */
+    float* terms_atom;                                              /* [B,N,15,5] */
+    float* terms_residue;                                           /* [B,N,5] */
+    float* energy_residue;                                          /* [B,N] */
+    int* pairs_atom; int* hbond_pairs_atom; int* hydrophobic_pairs_atom;    /* [B,N,15] */
+    int B, N, n_atoms;
+    float cutoff;                                                   /* > 0; 8.0 */
+    float w_gauss1, w_gauss2, w_repulsion, w_hydrophobic, w_hbond;  /* -0.0356, -0.00516, 0.840, -0.0351, -0.587 */
+} pf_interface_energy_args;
+int pf_interface_energy_fwd(const pf_interface_energy_args* a, pf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -239,6 +239,14 @@ class ContactsArgs(C.Structure):
                 ("n_atoms_y", _i), ("slot_mask", _i), ("contact_cutoff", C.c_float), ("interface_cutoff", C.c_float)]
 
 
+class InterfaceEnergyArgs(C.Structure):
+    _fields_ = [("pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("group", _fp), ("query", _fp), ("radius", _fp), ("types", _fp),
+                ("work", _fp), ("terms_atom", _fp), ("terms_residue", _fp), ("energy_residue", _fp), ("pairs_atom", _fp),
+                ("hbond_pairs_atom", _fp), ("hydrophobic_pairs_atom", _fp), ("B", _i), ("N", _i), ("n_atoms", _i),
+                ("cutoff", C.c_float), ("w_gauss1", C.c_float), ("w_gauss2", C.c_float), ("w_repulsion", C.c_float),
+                ("w_hydrophobic", C.c_float), ("w_hbond", C.c_float)]
+
+
 class EtBwdArgs(C.Structure):
     _fields_ = [("g_y", _fp), ("h1", _fp), ("h2", _fp), ("wfT_f16", _fp), ("w2T_f16", _fp), ("w1T_f16", _fp),
                 ("g_h2", _fp), ("g_h1", _fp), ("g_x", _fp), ("npairs", C.c_longlong), ("m1", _fp), ("m2", _fp)]
@@ -325,6 +333,7 @@ _SIGNATURES = {
     "pf_sidechain_compare_fwd": ([C.POINTER(SidechainCompareArgs), _fp], _i),
     "pf_lddt_fwd": ([C.POINTER(LddtArgs), _fp], _i),
     "pf_contacts_fwd": ([C.POINTER(ContactsArgs), _fp], _i),
+    "pf_interface_energy_fwd": ([C.POINTER(InterfaceEnergyArgs), _fp], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

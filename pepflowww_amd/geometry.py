@@ -1,11 +1,11 @@
 """Evaluation geometry on the device: thin wrappers that check their arguments, bind device pointers into one argument struct and
-launch one HIP entry point each (the kernels and their conventions are described in csrc/*.hip; DESIGN.md 3.8-3.15).
+launch one HIP entry point each (the kernels and their conventions are described in csrc/*.hip; DESIGN.md 3.8-3.16).
 
 Input families, one binding path each:
   pair work lists   point sets x [Bx,N,3] / y [By,N,3] with masks and `pairs` [P,2] -- `_pair_inputs`: superpose (and align, batch_align,
                     superpose_rmsd), tm_score, tm_align and their pairwise_* matrices (`_within_groups`, `_mirrored`);
   heavy-atom structures   pos [B,N,A,3], atom_mask [B,N,A] and per-residue [B,N] tensors -- `_structure`: structural_violations, sasa,
-                    torsion_angles and each side of sidechain_compare (dssp reads the same pos with a residue mask);
+                    torsion_angles, interface_energy and each side of sidechain_compare (dssp reads the same pos with a residue mask);
   both at once      two heavy-atom structure sets and a work list -- `_structure_pairs`: lddt (pf_lddt_fwd, the values of OpenFold's
                     lddt / lddt_ca, openfold/utils/loss.py:382-458) and interface_contacts (pf_contacts_fwd), which dockq combines
                     with `superpose` into Fnat, iRMSD, LRMSD and DockQ.
@@ -769,3 +769,142 @@ def dockq(x, y, pairs, group, contact_cutoff=5.0, interface_cutoff=10.0):
            "n_native_contacts": n_y, "n_sample_contacts": n_x, "n_shared_contacts": n_s, "n_interface": c["interface_y"].sum(1)}
     res.update(c)
     return res
+
+
+# ---- empirical interface energy ----------------------------------------------------------------------------------------------------
+# The functional form of AutoDock Vina's scoring function (Trott & Olson, J. Comput. Chem. 31, 2010) over heavy atoms.  Written from
+# the publication and checked against a float64 restatement (tests/energy_oracle.py) and hand-computed cases; NOT checked against
+# the Vina program, and neither Vina's output (no ligand preparation, no torsion tree, no hydrogens) nor Rosetta's dG_separated.
+ENERGY_MAX_N = 512          # PF_INTERFACE_ENERGY_MAX_N
+ENERGY_SLOTS = 15           # PF_INTERFACE_ENERGY_SLOTS
+ENERGY_TERMS = ("gauss1", "gauss2", "repulsion", "hydrophobic", "hbond")
+VINA_WEIGHTS = (-0.0356, -0.00516, 0.840, -0.0351, -0.587)
+XS_RADIUS = {"C": 1.9, "N": 1.8, "O": 1.7, "S": 2.0}
+TYPE_HYDROPHOBIC, TYPE_DONOR, TYPE_ACCEPTOR = 1, 2, 4       # the bits of interface_type_table
+# Stated from chemistry, resolved against the package's own atom-name table.  The covalent bonds of each side chain (CA-CB and
+# beyond; proline's ring closes on N); the backbone's N-CA, CA-C, C-O, C-OXT and the peptide bond C-N are added for every type.
+SIDE_CHAIN_BONDS = {
+    "ALA": "CA-CB", "GLY": "",
+    "CYS": "CA-CB CB-SG", "SER": "CA-CB CB-OG", "THR": "CA-CB CB-OG1 CB-CG2", "VAL": "CA-CB CB-CG1 CB-CG2",
+    "ASP": "CA-CB CB-CG CG-OD1 CG-OD2", "ASN": "CA-CB CB-CG CG-OD1 CG-ND2",
+    "GLU": "CA-CB CB-CG CG-CD CD-OE1 CD-OE2", "GLN": "CA-CB CB-CG CG-CD CD-OE1 CD-NE2",
+    "ILE": "CA-CB CB-CG1 CB-CG2 CG1-CD1", "LEU": "CA-CB CB-CG CG-CD1 CG-CD2", "MET": "CA-CB CB-CG CG-SD SD-CE",
+    "LYS": "CA-CB CB-CG CG-CD CD-CE CE-NZ", "ARG": "CA-CB CB-CG CG-CD CD-NE NE-CZ CZ-NH1 CZ-NH2", "PRO": "CA-CB CB-CG CG-CD CD-N",
+    "HIS": "CA-CB CB-CG CG-ND1 CG-CD2 ND1-CE1 CD2-NE2 CE1-NE2",
+    "PHE": "CA-CB CB-CG CG-CD1 CG-CD2 CD1-CE1 CD2-CE2 CE1-CZ CE2-CZ",
+    "TYR": "CA-CB CB-CG CG-CD1 CG-CD2 CD1-CE1 CD2-CE2 CE1-CZ CE2-CZ CZ-OH",
+    "TRP": "CA-CB CB-CG CG-CD1 CG-CD2 CD1-NE1 NE1-CE2 CD2-CE2 CD2-CE3 CE2-CZ2 CE3-CZ3 CZ2-CH2 CZ3-CH2"}
+# Hydrogen-bond donors and acceptors among the side-chain atoms, without hydrogens.  Convention: the tautomer of histidine is unknown
+# without hydrogens, so both of its ring nitrogens are donor and acceptor.  The backbone N is a donor except proline's; O and OXT
+# are acceptors.
+SIDE_CHAIN_DONORS = {"ARG": ("NE", "NH1", "NH2"), "ASN": ("ND2",), "GLN": ("NE2",), "LYS": ("NZ",), "TRP": ("NE1",), "SER": ("OG",),
+                     "THR": ("OG1",), "TYR": ("OH",), "HIS": ("ND1", "NE2")}
+SIDE_CHAIN_ACCEPTORS = {"ASP": ("OD1", "OD2"), "GLU": ("OE1", "OE2"), "ASN": ("OD1",), "GLN": ("OE1",), "SER": ("OG",), "THR": ("OG1",),
+                        "TYR": ("OH",), "HIS": ("ND1", "NE2")}
+_BACKBONE_BONDS = "N-CA CA-C C-O C-OXT"
+
+
+def xs_radius_table():
+    """-> [21,15] float32 CPU tensor: the XS radius (C 1.9, N 1.8, O 1.7, S 2.0 A) of heavy-atom slot s of residue type t, from the
+    first letter of the slot's atom name in the package's own table; 0 where the type has no such atom.  Row 20 (any type outside
+    0..19) has N, CA, C, O only, as in `vdw_radius_table`."""
+    from .preprocess import _tables
+    names = _tables()["atom_names"]
+    tab = torch.zeros(21, ENERGY_SLOTS)
+    for t in range(20):
+        for s in range(ENERGY_SLOTS):
+            if names[t][s]:
+                tab[t, s] = XS_RADIUS[names[t][s][0]]
+    for s, e in enumerate(_UNK_ELEMENTS):
+        tab[20, s] = XS_RADIUS[e]
+    return tab
+
+
+def interface_type_table():
+    """-> [21,15] uint8 CPU tensor of TYPE_HYDROPHOBIC | TYPE_DONOR | TYPE_ACCEPTOR per heavy-atom slot.  Hydrophobic: a carbon none
+    of whose covalent neighbours is N, O or S -- the neighbours from SIDE_CHAIN_BONDS, the backbone's bonds and the peptide bond (C is
+    bonded to the next residue's N, N to the previous C); sulfur itself is not hydrophobic.  Donors and acceptors: the backbone N
+    (not proline's), O, OXT, SIDE_CHAIN_DONORS and SIDE_CHAIN_ACCEPTORS.  Row 20: N (donor), CA, C, O (acceptor)."""
+    from .preprocess import _tables
+    t = _tables()
+    tab = torch.zeros(21, ENERGY_SLOTS, dtype=torch.uint8)
+    for name, side in list(SIDE_CHAIN_BONDS.items()) + [("UNK", "")]:
+        r = t["res_index"][name]
+        names = list(t["atom_names"][r]) if r < 20 else ["N", "CA", "C", "O"] + [""] * 11
+        polar = {"N": ["C"], "C": ["N"]}                    # the peptide bond's partner elements
+        for bond in (_BACKBONE_BONDS + " " + side).split():
+            u, v = bond.split("-")
+            if u in names and v in names:                   # (C-OXT: not in row 20)
+                polar.setdefault(u, []).append(v[0])
+                polar.setdefault(v, []).append(u[0])
+        for s, nm in enumerate(names):
+            if not nm:
+                continue
+            bits = 0
+            if nm[0] == "C" and not any(e in "NOS" for e in polar.get(nm, [])):
+                bits |= TYPE_HYDROPHOBIC
+            if (nm == "N" and name != "PRO") or nm in SIDE_CHAIN_DONORS.get(name, ()):
+                bits |= TYPE_DONOR
+            if nm in ("O", "OXT") or nm in SIDE_CHAIN_ACCEPTORS.get(name, ()):
+                bits |= TYPE_ACCEPTOR
+            tab[r, s] = bits
+    return tab
+
+
+def _weights(weights):
+    try:
+        w = tuple(float(v) for v in weights)
+    except (TypeError, ValueError):
+        w = ()
+    if len(w) != len(ENERGY_TERMS) or not all(math.isfinite(v) for v in w):
+        raise ValueError(f"weights must be five finite numbers, one per term of {ENERGY_TERMS}, got {weights!r}")
+    return w
+
+
+def interface_energy(pos, atom_mask, aa, group, query=None, cutoff=8.0, weights=VINA_WEIGHTS):
+    """pf_interface_energy_fwd: an empirical interface energy between the atoms of residues of different `group` bytes -- the
+    functional form of AutoDock Vina's scoring function (Trott & Olson, J. Comput. Chem. 2010) over heavy atoms (conventions:
+    csrc/interface_energy.hip).  It is written from the publication and checked against a float64 restatement in this tree and
+    against hand-computed cases; it has not been checked against the Vina program, and it is neither that program's output (no ligand
+    preparation, no torsion tree, no hydrogens) nor Rosetta's dG_separated.
+
+    pos [B,N,A,3] heavy atoms in the package's order, A >= 14, slots 0 .. min(A,15)-1 are read (pos_heavyatom passes as it is);
+    atom_mask [B,N,A]; aa [B,N] residue types in the package's numbering; group [B,N] (required): only pairs of atoms whose residues
+    have different group bytes are evaluated; N <= 512.  An atom takes part where its mask is set and its type has the slot
+    (`xs_radius_table`).  A pair counts when r < cutoff; d = r - R_i - R_j; terms ENERGY_TERMS: gauss1 exp(-(d/0.5)^2), gauss2
+    exp(-((d-3)/2)^2), repulsion d^2 for d < 0, hydrophobic (both atoms hydrophobic) 1 for d <= 0.5 falling to 0 at 1.5, hbond (a
+    donor and an acceptor, `interface_type_table`) 1 for d <= -0.7 falling to 0 at 0.  query [B,N] (optional): only atoms of query
+    residues are rows, every participating atom is still a partner; a participating atom that is not a row has counts -1 and zeros.
+    -> dict of device tensors: terms_atom [B,N,15,5] float32 (unweighted sums per row atom), terms_residue [B,N,5], pairs_atom,
+    hbond_pairs_atom, hydrophobic_pairs_atom [B,N,15] int32 (partners inside the cutoff, with hbond > 0, with hydrophobic > 0),
+    energy_residue [B,N] float32 = sum_k weights[k] terms_residue[k]; terms [B,5] and energy [B] float64: each pair shows in both of
+    its rows, so these are HALF the sums of terms_residue / energy_residue over all rows -- with `query` they are the plain sums
+    over the query rows (for a query that is one whole group, the same number)."""
+    if group is None:
+        raise ValueError("interface_energy needs `group` [B,N]: the energy is that between residues of different groups")
+    cutoff, w = _positive("cutoff", cutoff), _weights(weights)
+    dev, (B, N, A), pos, atom_mask, (aa, group, query) = _structure(pos, atom_mask, (
+        ("aa", aa, torch.int64), ("group", group, torch.uint8), ("query", query, torch.uint8)), max_n=ENERGY_MAX_N)
+    a = _capi.InterfaceEnergyArgs()
+    _bind_in(a, pos=pos, atom_mask=atom_mask, aa=aa, group=group, query=query)
+    S, T = ENERGY_SLOTS, len(ENERGY_TERMS)
+    f32 = lambda *shape: torch.empty(*shape, device=dev)  # noqa: E731
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = {"terms_atom": f32(B, N, S, T), "terms_residue": f32(B, N, T), "pairs_atom": i32(B, N, S), "hbond_pairs_atom": i32(B, N, S),
+           "hydrophobic_pairs_atom": i32(B, N, S), "energy_residue": f32(B, N)}
+    if B and N:
+        a.radius = _table("xs_radius", dev, xs_radius_table).data_ptr()
+        a.types = _table("interface_types", dev, interface_type_table).data_ptr()
+        _bind_out(a, out)
+        work = f32(B, N, 4)                         # the residue-sized workspace: centre and extent
+        a.work = work.data_ptr()
+        a.B, a.N, a.n_atoms, a.cutoff = B, N, A, cutoff
+        a.w_gauss1, a.w_gauss2, a.w_repulsion, a.w_hydrophobic, a.w_hbond = w
+        _capi.check(_capi.load().pf_interface_energy_fwd(C.byref(a), _capi.stream_ptr()), "pf_interface_energy_fwd")
+    else:
+        for v in out.values():
+            v.zero_()
+    half = 0.5 if query is None else 1.0
+    out["terms"] = out["terms_residue"].double().sum(1) * half
+    out["energy"] = out["energy_residue"].double().sum(1) * half
+    return out

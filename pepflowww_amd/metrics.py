@@ -8,10 +8,11 @@ and TM-score diversity (`structure_scores`); DSSP secondary structure and the se
 side-chain packing table, chi1-chi4 errors against the native and the share of residues with every chi within a tolerance
 (`sidechain_packing`); superposition-free local accuracy, lDDT with the values of OpenFold's lddt / lddt_ca
 (openfold/utils/loss.py:382-458), over the peptide and across the interface (`local_accuracy`); docking quality, Fnat, iRMSD, LRMSD and
-DockQ (`docking_quality`).
+DockQ (`docking_quality`); an empirical peptide-receptor interface energy, the functional form of AutoDock Vina's scoring function
+written from the publication and not checked against that program (`binding_energy`).
 
 Every per-residue, per-point and per-atom-pair operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd /
-pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
+pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
@@ -469,4 +470,44 @@ def docking_quality(final, batch, backbone="full_atom", contact_cutoff=5.0, inte
     has = ~torch.isnan(d["dockq"])
     out["dockq_pooled"] = _mean_of_defined(d["dockq"])
     out["success_rate"] = (has & (d["dockq"] >= 0.23)).sum().double() / has.sum().double()
+    return out
+
+
+ROT_PER_RESIDUE = 2         # phi and psi: the backbone's share of a generated residue in n_rot
+ROT_PENALTY = 0.0585        # Trott & Olson's weight of the rotatable-bond count
+
+
+def binding_energy(final, batch, backbone="full_atom", cutoff=8.0):
+    """An empirical affinity proxy for each sample: geometry.interface_energy -- the functional form of AutoDock Vina's scoring
+    function (Trott & Olson, J. Comput. Chem. 2010) over heavy atoms, with geometry.VINA_WEIGHTS -- between the peptide and its
+    receptor, for the sample's complex and for its native.  It is written from the publication and checked against a float64
+    restatement in this tree; it is not checked against the Vina program, and it stands in for, but is not, the Rosetta dG_separated
+    or FoldX value of the reference's evaluation.  final / batch and the two complexes are those of `structural_violations`; the
+    peptide is generate_mask & res_mask, the receptor the other residues of res_mask; padding residues have no atoms.  With
+    backbone="frames" the sample's generated residues have N, CA, C, O only: a backbone-only score, which the native (with its side
+    chains) is then not comparable with.
+
+    -> dict of device tensors.  Per sample [B], float64: energy, energy_native, delta = energy - energy_native; terms, terms_native
+    [B,5] (unweighted, geometry.ENERGY_TERMS); energy_per_rot = energy / (1 + 0.0585 n_rot).  n_hbonds, n_hydrophobic [B] int64: the
+    sample's atom pairs with hbond > 0 / hydrophobic > 0, summed over the peptide's rows.  n_rot [B] int64 = the sum over the
+    generated residues of (the number of chi angles of the sample's type, from the package's chi table, + 2 for phi and psi): this
+    package's convention for a peptide's rotatable bonds, not Vina's torsion tree.  clashing [B] bool: w_repulsion * repulsion >
+    |w_gauss1 * gauss1 + w_gauss2 * gauss2| on the sample's terms, i.e. the steric penalty outweighs the steric attraction.  Per
+    residue [B,L] float32: energy_residue, energy_residue_native (the rows of the peptide and of the receptor, each pair in both of
+    its rows; 0 elsewhere)."""
+    dev, res_mask, gen, _, sample, native = _complexes(final, batch, backbone)
+    out = {}
+    for tag, (pos, mask, aa) in (("", sample), ("_native", native)):
+        v = geometry.interface_energy(pos, mask & res_mask[:, :, None], aa, gen, cutoff=cutoff)
+        out["energy" + tag], out["terms" + tag], out["energy_residue" + tag] = v["energy"], v["terms"], v["energy_residue"]
+        if not tag:
+            over = lambda t: (t.to(torch.int64).sum(-1) * gen).sum(1)  # noqa: E731
+            out["n_hbonds"], out["n_hydrophobic"] = over(v["hbond_pairs_atom"]), over(v["hydrophobic_pairs_atom"])
+    out["delta"] = out["energy"] - out["energy_native"]
+    aa_s = sample[2]
+    n_chi = (geometry._table("chi_atoms", dev, geometry.chi_atom_table)[:, :, 0] >= 0).sum(1)          # [21]
+    out["n_rot"] = ((n_chi[torch.where((aa_s < 0) | (aa_s > 20), 20, aa_s)] + ROT_PER_RESIDUE) * gen).sum(1)
+    out["energy_per_rot"] = out["energy"] / (1.0 + ROT_PENALTY * out["n_rot"].double())
+    w, t = geometry.VINA_WEIGHTS, out["terms"]
+    out["clashing"] = w[2] * t[:, 2] > (w[0] * t[:, 0] + w[1] * t[:, 1]).abs()
     return out
