@@ -1144,6 +1144,58 @@ typedef struct {
 } pf_interface_energy_args;
 int pf_interface_energy_fwd(const pf_interface_energy_args* a, pf_stream_t stream);
 
+/* ---- restrained relaxation (ABI 64, added entry points) ---------------------------------------------------------------------------
+ * A restraint force field over the heavy atoms of a batch of structures and a monotone steepest-descent minimiser around it; the
+ * conventions are listed in csrc/relax.hip.  It is NOT Amber and NOT Rosetta: E = E_rest + E_intra + E_conn + E_clash is built from
+ * the clash overlap and the peptide-bond ideals of pf_violations_fwd and from the reference structure's own internal distances.
+ * Slots 0 .. min(n_atoms, 15) - 1 are read; an atom exists where atom_mask is set and radius has an entry for its type and slot; the
+ * existing atoms of movable residues move, every other atom is a fixed partner.
+ *   pf_relax_energy_fwd   one evaluation at pos: gradient [B,N,15,3] (zero on atoms that do not move), terms_atom [B,N,15,4] (rest,
+ *                         intra, conn, clash: every pair and connection counted once over the atoms), energy_atom [B,N,15] (optional),
+ *                         terms [B,4] and energy [B] (float64 sums in a fixed order).  Reads nothing below `energy`.
+ *   pf_relax_fwd          `steps` iterations from pos: trial y = x - alpha g on the moving atoms, accepted when E(y) <= E(x) in the
+ *                         float64 sums (alpha *= 1.2), else rejected (alpha *= 0.5); a sample whose max|g| <= gtol is frozen.  x, g, y
+ *                         [B,N,15,3] are the state (x: the result; atoms that do not move are copies of pos); gradient / terms_atom
+ *                         are the trial's; terms / energy the accepted state's; terms_initial [B,4]; energy_trace [B,steps+1];
+ *                         accepted [B,steps]; step_size [B,steps]; alpha, grad_max [B]; frozen, iterations [B].  1 + 2 (steps + 1)
+ *                         launches, no host readback.
+ * work: [B,N,4] floats, no initialisation needed.  No atomics, nothing pair-sized, one writer per output and every sum in a fixed
+ * order: bit-identical from run to run and independent of the rest of the batch.  N > PF_RELAX_MAX_N or B > 65535 -> PF_E_TOOLARGE. */
+#define PF_RELAX_MAX_N 512
+#define PF_RELAX_SLOTS 15
+#define PF_RELAX_TERMS 4
+typedef struct {
+    const float* pos;                                               /* [B,N,n_atoms,3] */
+    const float* ref_pos;                                           /* [B,N,n_atoms,3] the restraint and internal-geometry reference */
+    const unsigned char* atom_mask;                                 /* [B,N,n_atoms] */
+    const int64_t* aa;                                              /* [B,N] */
+    const int* residue_index;                                       /* [B,N] */
+    const unsigned char* movable;                                   /* [B,N] */
+    const float* radius;                                            /* [21,15] van der Waals radii, 0: the type has no such atom */
+    const int* pair_mask;                                           /* [21,15] bit b of (t, a): slots a and b of type t are restrained */
+    float* work;                                                    /* [B,N,4] */
+    float* gradient;                                                /* [B,N,15,3] */
+    float* terms_atom;                                              /* [B,N,15,4] */
+    float* energy_atom;                                             /* [B,N,15] optional */
+    double* terms;                                                  /* [B,4] */
+    double* energy;                                                 /* [B] */
+    float* x; float* g; float* y;                                   /* [B,N,15,3] pf_relax_fwd: accepted positions, gradient; trial */
+    float* alpha;                                                   /* [B] */
+    int* frozen;                                                    /* [B] */
+    double* terms_initial;                                          /* [B,4] */
+    double* energy_trace;                                           /* [B,steps+1] */
+    unsigned char* accepted;                                        /* [B,steps] */
+    float* step_size;                                               /* [B,steps] */
+    float* grad_max;                                                /* [B] */
+    int* iterations;                                                /* [B] */
+    int B, N, n_atoms, pro, steps;
+    float k_rest, k_intra, k_bond, k_angle, k_clash;                /* > 0; 10, 300, 300, 150, 200 */
+    float clash_overlap_tolerance, clash_margin;                    /* 1.5, 0.2 */
+    float step0, gtol;                                              /* > 0, >= 0; 0.002, 0 */
+} pf_relax_args;
+int pf_relax_energy_fwd(const pf_relax_args* a, pf_stream_t stream);
+int pf_relax_fwd(const pf_relax_args* a, pf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -247,6 +247,16 @@ class InterfaceEnergyArgs(C.Structure):
                 ("w_hydrophobic", C.c_float), ("w_hbond", C.c_float)]
 
 
+class RelaxArgs(C.Structure):
+    _fields_ = [("pos", _fp), ("ref_pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("residue_index", _fp), ("movable", _fp),
+                ("radius", _fp), ("pair_mask", _fp), ("work", _fp), ("gradient", _fp), ("terms_atom", _fp), ("energy_atom", _fp),
+                ("terms", _fp), ("energy", _fp), ("x", _fp), ("g", _fp), ("y", _fp), ("alpha", _fp), ("frozen", _fp),
+                ("terms_initial", _fp), ("energy_trace", _fp), ("accepted", _fp), ("step_size", _fp), ("grad_max", _fp),
+                ("iterations", _fp), ("B", _i), ("N", _i), ("n_atoms", _i), ("pro", _i), ("steps", _i),
+                ("k_rest", C.c_float), ("k_intra", C.c_float), ("k_bond", C.c_float), ("k_angle", C.c_float), ("k_clash", C.c_float),
+                ("clash_overlap_tolerance", C.c_float), ("clash_margin", C.c_float), ("step0", C.c_float), ("gtol", C.c_float)]
+
+
 class EtBwdArgs(C.Structure):
     _fields_ = [("g_y", _fp), ("h1", _fp), ("h2", _fp), ("wfT_f16", _fp), ("w2T_f16", _fp), ("w1T_f16", _fp),
                 ("g_h2", _fp), ("g_h1", _fp), ("g_x", _fp), ("npairs", C.c_longlong), ("m1", _fp), ("m2", _fp)]
@@ -334,6 +344,8 @@ _SIGNATURES = {
     "pf_lddt_fwd": ([C.POINTER(LddtArgs), _fp], _i),
     "pf_contacts_fwd": ([C.POINTER(ContactsArgs), _fp], _i),
     "pf_interface_energy_fwd": ([C.POINTER(InterfaceEnergyArgs), _fp], _i),
+    "pf_relax_energy_fwd": ([C.POINTER(RelaxArgs), _fp], _i),
+    "pf_relax_fwd": ([C.POINTER(RelaxArgs), _fp], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -908,3 +908,185 @@ def interface_energy(pos, atom_mask, aa, group, query=None, cutoff=8.0, weights=
     out["terms"] = out["terms_residue"].double().sum(1) * half
     out["energy"] = out["energy_residue"].double().sum(1) * half
     return out
+
+
+# A restraint force field and a monotone minimiser around it (conventions: csrc/relax.hip).  It is NOT Amber and NOT Rosetta's
+# FastRelax: no hydrogens, no electrostatics, no torsion terms, no fitted parameter.  Its terms are the clash overlap and the
+# peptide-bond ideals of `structural_violations` plus the input structure's own internal distances; it stands where the reference's
+# evaluation relaxes a sample before scoring it (eval/energy.py, openfold/np/relax/amber_minimize.py) in role only, not in values.
+RELAX_MAX_N = 512           # PF_RELAX_MAX_N
+RELAX_SLOTS = 15            # PF_RELAX_SLOTS
+RELAX_TERMS = ("rest", "intra", "conn", "clash")
+# none of the stiffnesses is fitted to anything; k_rest is the restraint stiffness of amber_minimize.py
+RELAX_DEFAULTS = dict(k_rest=10.0, k_intra=300.0, k_bond=300.0, k_angle=150.0, k_clash=200.0, clash_overlap_tolerance=1.5,
+                      clash_margin=0.2, step0=0.002, gtol=0.0)
+
+
+def bond_table():
+    """-> [21,15,15] bool CPU tensor: the covalent bonds between the heavy-atom slots of residue type t, stated from chemistry as
+    atom-name pairs (SIDE_CHAIN_BONDS and the backbone's N-CA, CA-C, C-O, C-OXT; proline's ring closes with CD-N) and resolved
+    against the package's own atom-name table.  Row 20 (any type outside 0..19): N-CA, CA-C, C-O."""
+    from .preprocess import _tables
+    t = _tables()
+    tab = torch.zeros(21, RELAX_SLOTS, RELAX_SLOTS, dtype=torch.bool)
+    for name, side in list(SIDE_CHAIN_BONDS.items()) + [("UNK", "")]:
+        r = t["res_index"][name]
+        names = list(t["atom_names"][r][:RELAX_SLOTS]) if r < 20 else ["N", "CA", "C", "O"] + [""] * 11
+        for bond in (_BACKBONE_BONDS + " " + side).split():
+            u, v = bond.split("-")
+            if u in names and v in names:                   # (C-OXT: not in row 20)
+                tab[r, names.index(u), names.index(v)] = tab[r, names.index(v), names.index(u)] = True
+    return tab
+
+
+def restrained_pair_table():
+    """-> [21,15,15] bool CPU tensor: the atom pairs of a residue whose distance `relax` holds at the reference's: at most two bonds
+    apart in `bond_table` (bonds and bond angles), or both in the same rigid group (atom14_group of data/rigid_groups.npz; OXT counts
+    with O) -- so rings and planar groups stay rigid, and psi and chi1-chi4 stay free.  Symmetric, no diagonal, existing slots only."""
+    import os
+
+    import numpy as np
+
+    from .preprocess import _HERE, _tables
+    names = _tables()["atom_names"]
+    group = torch.from_numpy(np.load(os.path.join(_HERE, "data", "rigid_groups.npz"))["atom14_group"][:21]).to(torch.int64)
+    group[20, 3] = group[0, 3]                              # (the file's row 20 is empty: O turns with psi there too)
+    group = torch.cat([group, group[:, 3:4]], 1)            # OXT with O
+    bonds = bond_table()
+    two = bonds | ((bonds.to(torch.int32) @ bonds.to(torch.int32)) > 0)
+    has = torch.tensor([[bool(names[t][s]) for s in range(RELAX_SLOTS)] for t in range(20)] + [[True] * 4 + [False] * 11])
+    tab = (two | (group[:, :, None] == group[:, None, :])) & has[:, :, None] & has[:, None, :]
+    return tab & ~torch.eye(RELAX_SLOTS, dtype=torch.bool)
+
+
+def _pair_mask_table():
+    """-> [21,15] int32: bit b of (t, a) = restrained_pair_table()[t, a, b], the form the kernel reads"""
+    bits = (1 << torch.arange(RELAX_SLOTS, dtype=torch.int64))
+    return (restrained_pair_table().to(torch.int64) * bits).sum(-1).to(torch.int32)
+
+
+def _relax_params(params, steps=None):
+    p = dict(RELAX_DEFAULTS)
+    for k, v in params.items():
+        if k not in p:
+            raise ValueError(f"unknown parameter {k!r}; the parameters are {tuple(p)}")
+        p[k] = v
+    for k in p:
+        try:
+            v = float(p[k])
+        except (TypeError, ValueError):
+            v = float("nan")
+        want = "finite" if k in ("clash_overlap_tolerance", "clash_margin") else ">= 0" if k == "gtol" else "> 0"
+        if not math.isfinite(v) or (want == ">= 0" and v < 0) or (want == "> 0" and not v > 0):
+            raise ValueError(f"{k} must be a number {want}, got {p[k]!r}")
+        p[k] = v
+    if steps is not None and (not isinstance(steps, int) or isinstance(steps, bool) or steps < 0):
+        raise ValueError(f"steps must be an integer >= 0, got {steps!r}")
+    return p
+
+
+def _relax_args(pos, ref_pos, atom_mask, aa, residue_index, movable, p):
+    """the checked and bound inputs of pf_relax_energy_fwd / pf_relax_fwd -> (args, device, (B, N, A), the tensors to keep alive)"""
+    if movable is None or residue_index is None:
+        raise ValueError("relax needs residue_index [B,N] and movable [B,N]")
+    dev, (B, N, A), pos, atom_mask, (aa, residue_index, movable) = _structure(pos, atom_mask, (
+        ("aa", aa, torch.int64), ("residue_index", residue_index, torch.int32), ("movable", movable, torch.uint8)), max_n=RELAX_MAX_N)
+    if ref_pos is None:
+        ref_pos = pos
+    else:
+        if not isinstance(ref_pos, torch.Tensor) or tuple(ref_pos.shape) != (B, N, A, 3):
+            raise ValueError(f"ref_pos must have the shape of pos {(B, N, A, 3)}, got {tuple(getattr(ref_pos, 'shape', ()))}")
+        ref_pos = _f32(ref_pos, dev)
+    a = _capi.RelaxArgs()
+    _bind_in(a, pos=pos, ref_pos=ref_pos, atom_mask=atom_mask, aa=aa, residue_index=residue_index, movable=movable)
+    a.B, a.N, a.n_atoms, a.pro = B, N, A, _proline()
+    for k in RELAX_DEFAULTS:
+        setattr(a, k, p[k])
+    return a, dev, (B, N, A), [pos, ref_pos, atom_mask, aa, residue_index, movable]
+
+
+def _relax_tables(a, dev):
+    a.radius = _table("sasa_radius", dev, sasa_radius_table).data_ptr()
+    a.pair_mask = _table("relax_pair_mask", dev, _pair_mask_table).data_ptr()
+
+
+def relax_energy(pos, ref_pos, atom_mask, aa, residue_index, movable, **params):
+    """pf_relax_energy_fwd: one evaluation of the restraint force field of `relax` and of its analytic gradient (conventions:
+    csrc/relax.hip).  Not Amber and not Rosetta: E = E_rest + E_intra + E_conn + E_clash over heavy atoms, from the clash overlap and
+    peptide-bond ideals of `structural_violations` and the internal distances of ref_pos.
+
+    pos, ref_pos [B,N,A,3] heavy atoms in the package's order, A >= 14, slots 0 .. min(A,15)-1 are read; atom_mask [B,N,A]; aa [B,N]
+    residue types; residue_index [B,N] integers (a peptide bond joins n and n + 1 where it grows by exactly 1; atoms of equal index
+    never clash); movable [B,N]: the residues whose existing atoms move, every other atom is a fixed partner; N <= 512.  An atom
+    exists where its mask is set and `sasa_radius_table` has the slot.  params: RELAX_DEFAULTS (k_rest, k_intra, k_bond, k_angle,
+    k_clash > 0; clash_overlap_tolerance, clash_margin).
+    -> dict of device tensors: terms [B,4] float64 (RELAX_TERMS: rest, intra, conn, clash), energy [B] float64, gradient [B,N,15,3]
+    float32 (zero on atoms that do not move), energy_atom [B,N,15] float32, terms_atom [B,N,15,4] float32 (every pair and connection
+    counted once over the atoms)."""
+    p = _relax_params(params)
+    a, dev, (B, N, A), keep = _relax_args(pos, ref_pos, atom_mask, aa, residue_index, movable, p)
+    S, T = RELAX_SLOTS, len(RELAX_TERMS)
+    f32 = lambda *shape: torch.empty(*shape, device=dev)  # noqa: E731
+    f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)  # noqa: E731
+    out = {"terms": f64(B, T), "energy": f64(B), "gradient": f32(B, N, S, 3), "energy_atom": f32(B, N, S), "terms_atom": f32(B, N, S, T)}
+    if B and N:
+        _relax_tables(a, dev)
+        _bind_out(a, out)
+        work = f32(B, N, 4)                         # the residue-sized workspace: centre and extent
+        a.work = work.data_ptr()
+        _capi.check(_capi.load().pf_relax_energy_fwd(C.byref(a), _capi.stream_ptr()), "pf_relax_energy_fwd")
+    else:
+        for v in out.values():
+            v.zero_()
+    return out
+
+
+def relax(pos, atom_mask, aa, residue_index, movable, steps=200, **params):
+    """pf_relax_fwd: restrained relaxation of heavy-atom structures on the device -- `steps` iterations of a monotone steepest descent
+    on the energy of `relax_energy` with ref_pos = pos (conventions: csrc/relax.hip).  It removes clashes and mends peptide bonds
+    while bonds, angles and rings keep the input's geometry and every atom is tethered to where it started; it is NOT Amber
+    (amber_minimize.py) and NOT Rosetta's FastRelax, and stands for them in role only.
+
+    Arguments as `relax_energy`; steps >= 0; params: RELAX_DEFAULTS, also step0 > 0 (the first step size) and gtol >= 0.  Per sample:
+    trial y = x - alpha g on the moving atoms, accepted when E(y) <= E(x) in the float64 sums (alpha *= 1.2), else rejected (alpha *=
+    0.5); once max|g| <= gtol the sample is frozen.  Samples are independent of each other; nothing is read back during the loop.
+    -> dict of device tensors: pos [B,N,A,3] float32 (atoms that do not move and slots >= 15 are bit-identical copies of the input);
+    terms_initial, terms_final [B,4] float64; energy_trace [B,steps+1] float64 (the accepted energy after each iteration, [0]: the
+    input's); accepted [B,steps] bool; step_size [B,steps] float32 (the alpha of trial i; a frozen sample repeats its last);
+    grad_max [B] float32 (max|g| of the accepted state); iterations [B] int32 (iterations run before freezing); rmsd [B] float64 over
+    the moving atoms against the input (0 without any)."""
+    p = _relax_params(params, steps)
+    a, dev, (B, N, A), keep = _relax_args(pos, None, atom_mask, aa, residue_index, movable, p)
+    pos, atom_mask, aa, movable = keep[0], keep[2], keep[3], keep[5]
+    S, T = RELAX_SLOTS, len(RELAX_TERMS)
+    f32 = lambda *shape: torch.empty(*shape, device=dev)  # noqa: E731
+    f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)  # noqa: E731
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = {"terms_initial": f64(B, T), "terms": f64(B, T), "energy_trace": f64(B, steps + 1),
+           "accepted": torch.empty(B, steps, dtype=torch.uint8, device=dev), "step_size": f32(B, steps), "grad_max": f32(B),
+           "iterations": i32(B)}
+    x = f32(B, N, S, 3)
+    if B and N:
+        _relax_tables(a, dev)
+        _bind_out(a, out)
+        state = {"x": x, "g": f32(B, N, S, 3), "y": f32(B, N, S, 3), "gradient": f32(B, N, S, 3), "terms_atom": f32(B, N, S, T),
+                 "work": f32(B, N, 4), "energy": f64(B), "alpha": f32(B), "frozen": i32(B)}
+        _bind_out(a, state)
+        a.steps = steps
+        _capi.check(_capi.load().pf_relax_fwd(C.byref(a), _capi.stream_ptr()), "pf_relax_fwd")
+        new = pos.clone()
+        new[:, :, :S] = x[:, :, :min(A, S)]
+    else:
+        for v in out.values():
+            v.zero_()
+        new = pos.clone()
+    out["terms_final"] = out.pop("terms")
+    _as_bool(out, "accepted")
+    tab = _table("sasa_radius", dev, sasa_radius_table)
+    n = min(A, S)
+    moving = (atom_mask[:, :, :n] != 0) & (tab[torch.where((aa < 0) | (aa > 20), 20, aa)][:, :, :n] > 0) & (movable != 0)[:, :, None]
+    sq = ((new[:, :, :n].double() - pos[:, :, :n].double()) ** 2).sum(-1) * moving
+    cnt = moving.sum((1, 2)).double()
+    out["rmsd"] = torch.sqrt(sq.sum((1, 2)) / cnt.clamp(min=1.0))
+    out["pos"] = new
+    return out

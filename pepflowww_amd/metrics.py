@@ -12,7 +12,7 @@ DockQ (`docking_quality`); an empirical peptide-receptor interface energy, the f
 written from the publication and not checked against that program (`binding_energy`).
 
 Every per-residue, per-point and per-atom-pair operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd /
-pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
+pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_relax_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
@@ -510,4 +510,38 @@ def binding_energy(final, batch, backbone="full_atom", cutoff=8.0):
     out["energy_per_rot"] = out["energy"] / (1.0 + ROT_PENALTY * out["n_rot"].double())
     w, t = geometry.VINA_WEIGHTS, out["terms"]
     out["clashing"] = w[2] * t[:, 2] > (w[0] * t[:, 0] + w[1] * t[:, 1]).abs()
+    return out
+
+
+def relax_samples(final, batch, backbone="full_atom", steps=200, **params):
+    """Restrained relaxation of each sample's complex on the device (geometry.relax: a restraint force field from the clash overlap
+    and peptide-bond ideals of `structural_violations` plus the sample's own internal distances, and a monotone minimiser; NOT Amber
+    and NOT Rosetta's FastRelax, whose place before the energy it takes in role only), with the clash counts and the interface
+    energy before and after.  final / batch and the sample's complex are those of `binding_energy`; the generated residues move, the
+    receptor is fixed; steps and params go to geometry.relax.
+
+    -> dict of device tensors: pos_heavyatom [B,L,15,3] float32 (the receptor's atoms bit-identical to the rebuilt complex, i.e. to
+    batch["pos_heavyatom"]), mask_heavyatom [B,L,15] bool, rmsd_heavy [B] float64 (the generated residues' atoms against the
+    unrelaxed sample); terms_before, terms_after [B,4] float64 (geometry.RELAX_TERMS), relax_energy_before, relax_energy_after,
+    energy_trace [B,steps+1], accepted [B,steps], iterations [B]; clash_atoms_before, clash_atoms_after, clash_atoms_cross_before,
+    clash_atoms_cross_after [B] int64: the generated residues' atoms that geometry.structural_violations flags, against any other
+    residue and against the receptor; energy, energy_relaxed [B] float64 and clashing, clashing_relaxed [B] bool: geometry.
+    interface_energy between peptide and receptor and `binding_energy`'s clashing flag, on the sample and on the relaxed complex."""
+    _check_backbone(backbone)
+    geometry._relax_params(params, steps)                   # checked before final / batch are touched
+    dev, res_mask, gen, index, (pos, mask, aa), _ = _complexes(final, batch, backbone, index=True)
+    mask = mask & res_mask[:, :, None]
+    r = geometry.relax(pos, mask, aa, index, gen, steps=steps, **params)
+    out = {"pos_heavyatom": r["pos"], "mask_heavyatom": mask, "rmsd_heavy": r["rmsd"], "terms_before": r["terms_initial"],
+           "terms_after": r["terms_final"], "relax_energy_before": r["energy_trace"][:, 0], "relax_energy_after": r["energy_trace"][:, -1],
+           "energy_trace": r["energy_trace"], "accepted": r["accepted"], "iterations": r["iterations"]}
+    w = geometry.VINA_WEIGHTS
+    for tag, etag, p in (("_before", "", pos), ("_after", "_relaxed", r["pos"])):
+        v = geometry.structural_violations(p, mask, aa, index, query=gen, group=gen)
+        out["clash_atoms" + tag] = (v["clash_atom"] & gen[:, :, None]).sum((1, 2))
+        out["clash_atoms_cross" + tag] = (v["clash_atom_cross"] & gen[:, :, None]).sum((1, 2))
+        e = geometry.interface_energy(p, mask, aa, gen)
+        t = e["terms"]
+        out["energy" + etag] = e["energy"]
+        out["clashing" + etag] = w[2] * t[:, 2] > (w[0] * t[:, 0] + w[1] * t[:, 1]).abs()
     return out

@@ -1,0 +1,239 @@
+"""CPU checks of the restrained relaxation (a restraint force field and a monotone minimiser; not Amber, not Rosetta): the bond table
+against the reference's recorded bond matrix, the restrained-pair table's properties, the ctypes struct layout against the header, the
+exported symbols, the wrappers' argument checks, and the numpy oracle (relax_oracle.py): its gradient against central differences of
+its energy, its minimiser against the hand-computed minima of relax_cases.py, and the conditions on the seeds of the GPU tests."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(__file__))
+import relax_cases as RC  # noqa: E402
+import relax_oracle as RO  # noqa: E402
+from test_lddt_cpu import HEADER, header_fields  # noqa: E402
+from pepflowww_amd import _capi, build, geometry, metrics  # noqa: E402
+from pepflowww_amd.preprocess import _tables  # noqa: E402
+
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "heavyatom_bonds.npz")
+
+
+# ---- the tables ----------------------------------------------------------------------------------------------------------------------
+
+def test_bond_table_equals_the_recorded_bond_matrix():
+    g = np.load(GOLDEN)
+    tab, t = geometry.bond_table(), _tables()
+    assert tab.shape == (21, 15, 15) and tab.dtype == torch.bool
+    # the recorded matrix is in the package's residue and atom order
+    assert [str(n) for n in g["resnames"]] == [n for n, i in sorted(t["res_index"].items(), key=lambda kv: kv[1])]
+    for r in range(20):
+        assert [str(n) for n in g["atom_names"][r]] == list(t["atom_names"][r][:15]), r
+    assert np.array_equal(tab[:20].numpy(), g["bonds"][:20])
+    # the reference lists no bond for UNK; row 20 is the backbone's N-CA, CA-C, C=O
+    assert not g["bonds"][20].any()
+    want = torch.zeros(15, 15, dtype=torch.bool)
+    for a, b in ((0, 1), (1, 2), (2, 3)):
+        want[a, b] = want[b, a] = True
+    assert torch.equal(tab[20], want)
+    pro, names = t["res_index"]["PRO"], t["atom_names"]
+    assert tab[pro, names[pro].index("CD"), 0] and tab[0, 2, 14]                 # proline's CD-N, C-OXT
+
+
+def test_restrained_pair_table():
+    tab, bonds, t = geometry.restrained_pair_table(), geometry.bond_table(), _tables()
+    assert tab.shape == (21, 15, 15) and tab.dtype == torch.bool
+    assert torch.equal(tab, tab.transpose(1, 2)) and not tab.diagonal(dim1=1, dim2=2).any()
+    assert (tab | ~bonds).all()                                                  # every bond
+    for res, r in t["res_index"].items():
+        names = list(t["atom_names"][r][:15]) if r < 20 else ["N", "CA", "C", "O"] + [""] * 11
+        absent = torch.tensor([not n for n in names])
+        assert not tab[r][absent].any() and not tab[r][:, absent].any(), res
+        assert not tab[r, 0, 3], res                                             # N-O: psi is free
+        if "CG" in names and res != "PRO":                                       # N-CG: chi1 is free (proline's ring closes on N)
+            assert not tab[r, 0, names.index("CG")], res
+        for k in range(4):                                                       # the end atoms of every chi are free of each other
+            a, _, _, d = (int(v) for v in geometry.chi_atom_table()[r, k])
+            if a >= 0 and res != "PRO":
+                assert not tab[r, a, d], (res, k)
+    phe = t["res_index"]["PHE"]
+    cg, *ring = [t["atom_names"][phe].index(n) for n in ("CG", "CD1", "CD2", "CE1", "CE2", "CZ")]
+    assert all(tab[phe, a, b] for a in ring for b in ring if a != b)             # a ring is rigid: one group beyond CG,
+    assert all(tab[phe, cg, a] for a in ring[:4]) and not tab[phe, cg, ring[4]]  # which holds CD1, CD2 (bonds), CE1, CE2 (angles)
+    mask = geometry._pair_mask_table()
+    assert mask.shape == (21, 15) and mask.dtype == torch.int32
+    assert all(bool(mask[r, a] >> b & 1) == bool(tab[r, a, b]) for r in (0, 12, 18, 20) for a in range(15) for b in range(15))
+    assert geometry.RELAX_TERMS == RO.TERMS and geometry.RELAX_DEFAULTS == RO.DEFAULTS
+
+
+# ---- the C ABI -----------------------------------------------------------------------------------------------------------------------
+
+def test_struct_layout_agrees_with_the_header():
+    cls = _capi.RelaxArgs
+    assert [(n, t) for n, t in cls._fields_] == header_fields("pf_relax_args")
+    last = cls._fields_[-1][0]
+    assert getattr(cls, last).offset + 4 <= C.sizeof(cls) and C.sizeof(cls) % 8 == 0
+
+
+def test_header_keeps_the_abi_version_and_the_order():
+    text = open(HEADER).read()
+    assert "#define PF_ABI_VERSION 64" in text and _capi.ABI_VERSION == 64
+    assert text.index("} pf_interface_energy_args;") < text.index("} pf_relax_args;")
+    assert text.index("int pf_interface_energy_fwd(") < text.index("int pf_relax_energy_fwd(") < text.index("int pf_relax_fwd(")
+    assert "#define PF_RELAX_MAX_N 512" in text and geometry.RELAX_MAX_N == 512
+    assert "#define PF_RELAX_SLOTS 15" in text and geometry.RELAX_SLOTS == 15
+    assert "#define PF_RELAX_TERMS 4" in text and len(geometry.RELAX_TERMS) == 4
+    assert build.SOURCES[-1] == "relax.hip" and build.SOURCES[-2] == "interface_energy.hip"
+    assert _capi.EXPORTED_SYMBOLS[-3:] == ("pf_interface_energy_fwd", "pf_relax_energy_fwd", "pf_relax_fwd")
+
+
+def test_library_exports_the_entry_points():
+    lib = _capi.load()
+    assert lib.pf_abi_version() == _capi.ABI_VERSION == 64
+    for f in (lib.pf_relax_energy_fwd, lib.pf_relax_fwd):
+        assert f(None, None) == -1
+        assert f(C.byref(_capi.RelaxArgs()), None) == -1
+
+
+def test_wrapper_argument_checks():
+    B, N = 2, 5
+    pos, mask = torch.zeros(B, N, 15, 3), torch.ones(B, N, 15, dtype=torch.bool)
+    aa, idx = torch.zeros(B, N, dtype=torch.int64), torch.arange(N).repeat(B, 1)
+    mov = torch.ones(B, N, dtype=torch.bool)
+    e = lambda *a, **kw: geometry.relax_energy(*a, **kw)  # noqa: E731
+    r = lambda p, *a, **kw: geometry.relax(p, *a, **kw)  # noqa: E731
+    for args in ((torch.zeros(B, N, 4, 3), mask, aa, idx, mov), (pos[0], mask, aa, idx, mov), (pos, mask[:, :, :14], aa, idx, mov),
+                 (pos, mask, aa[:, :4], idx, mov), (pos, mask, aa, idx[:1], mov), (pos, mask, aa, idx, mov[:, :3]),
+                 (pos, mask, aa, idx, None), (pos, mask, aa, None, mov)):
+        with pytest.raises(ValueError):
+            r(*args)
+        with pytest.raises(ValueError):
+            e(args[0], args[0], *args[1:])
+    with pytest.raises(ValueError):
+        e(pos, pos[:, :, :14], mask, aa, idx, mov)                               # ref_pos of another shape
+    for kw in (dict(k_rest=0.0), dict(k_intra=-1.0), dict(k_bond=float("nan")), dict(k_angle=float("inf")), dict(k_clash=0.0),
+               dict(clash_margin=float("nan")), dict(clash_overlap_tolerance=float("inf")), dict(k_spring=1.0), dict(k_rest=None)):
+        with pytest.raises(ValueError):
+            e(pos, pos, mask, aa, idx, mov, **kw)
+        with pytest.raises(ValueError):
+            r(pos, mask, aa, idx, mov, **kw)
+    for kw in (dict(step0=0.0), dict(step0=float("nan")), dict(gtol=-1.0), dict(steps=-1), dict(steps=2.5), dict(steps=True)):
+        with pytest.raises(ValueError):
+            r(pos, mask, aa, idx, mov, **kw)
+    big = 513                                               # above the kernel's bound
+    with pytest.raises(ValueError):
+        r(torch.zeros(1, big, 15, 3), torch.ones(1, big, 15, dtype=torch.bool), torch.zeros(1, big, dtype=torch.int64),
+          torch.arange(big)[None], torch.ones(1, big, dtype=torch.bool))
+    with pytest.raises(_capi.PepflowHipError):              # CPU tensors: no fall-back
+        r(pos, mask, aa, idx, mov)
+    with pytest.raises(_capi.PepflowHipError):
+        e(pos, pos, mask, aa, idx, mov)
+    with pytest.raises(ValueError):
+        metrics.relax_samples({}, {}, backbone="atoms")
+    with pytest.raises(ValueError):
+        metrics.relax_samples({}, {}, steps=-3)
+
+
+# ---- the oracle ----------------------------------------------------------------------------------------------------------------------
+
+def _args(case, b, movable=None):
+    return (case["ref_pos"][b], case["atom_mask"][b], case["aa"][b], case["residue_index"][b],
+            case["movable"][b] if movable is None else movable)
+
+
+def test_oracle_gradient_matches_central_differences():
+    """step 1e-6, tolerance 1e-6 relative to the stiffness scale (the largest stiffness, 300), in float64; every term takes part"""
+    case = RC.make_case(4001, 3, 17)
+    for b, movable in ((1, None), (2, np.ones(17, bool))):
+        args = _args(case, b, movable)
+        x = case["pos"][b].astype(np.float64)
+        o = RO.energy(x, *args)
+        assert (o["terms"] > 0).all(), o["terms"]
+        rng, worst = np.random.default_rng(b), 0.0
+        mv = np.argwhere(o["moving"])
+        for r, s in mv[rng.choice(len(mv), 25, replace=False)]:
+            for k in range(3):
+                xp, xm = x.copy(), x.copy()
+                xp[r, s, k] += 1e-6
+                xm[r, s, k] -= 1e-6
+                fd = (RO.energy(xp, *args)["energy"] - RO.energy(xm, *args)["energy"]) / 2e-6
+                worst = max(worst, abs(fd - o["gradient"][r, s, k]))
+        assert worst <= 1e-6 * 300.0, worst
+        assert not o["gradient"][~o["moving"]].any()
+        assert abs(o["terms_atom"].sum() - o["energy"]) <= 1e-9 * o["energy"]
+
+
+def test_oracle_counts_every_pair_once():
+    """the clash term against every unordered pair written out, and the moving atoms' share of a connection"""
+    case = RC.make_case(4002, 3, 33)
+    b = 2
+    o = RO.energy(case["pos"][b].astype(np.float64), *_args(case, b))
+    rad_t, _ = RO.tables()
+    aa, idx, mov = case["aa"][b], case["residue_index"][b], case["movable"][b]
+    rad = rad_t[np.where((aa < 0) | (aa > 20), 20, aa)]
+    ex = case["atom_mask"][b] & (rad > 0)
+    x, total = case["pos"][b].astype(np.float64), 0.0
+    atoms = [(r, s) for r in range(33) for s in range(15) if ex[r, s]]
+    for i, (r, s) in enumerate(atoms):
+        for q, t in atoms[i + 1:]:
+            if idx[r] == idx[q] or not (mov[r] or mov[q]) or (s == 5 and t == 5):
+                continue
+            if (s == 2 and t == 0 and idx[r] + 1 == idx[q]) or (s == 0 and t == 2 and idx[q] + 1 == idx[r]):
+                continue
+            d = np.sqrt(1e-10 + ((x[r, s] - x[q, t]) ** 2).sum())
+            total += 0.5 * 200.0 * max(rad[r, s] + rad[q, t] - 1.5 + 0.2 - d, 0.0) ** 2
+    assert total > 0 and abs(o["terms"][3] - total) <= 1e-9 * total
+
+
+def test_oracle_minimiser_reaches_the_hand_computed_minima():
+    case, x0, disp = RC.two_atoms()
+    assert abs(disp - 200.0 * 0.5 / 210.0) < 1e-15
+    m = RO.minimise(*_args(case, 0), 200)
+    assert abs(m["pos"][1, 1, 0] - x0 - disp) <= 1e-4 and not m["pos"][0].any() and not m["pos"][1, 1, 1:].any()
+    assert (np.diff(m["energy_trace"]) <= 0).all()
+
+    case, axis, t = RC.stretched_bond()
+    first = RO.energy(case["pos"][0].astype(np.float64), *_args(case, 0))
+    assert first["terms"][3] == 0 and abs(first["terms"][2] - 0.5 * 300.0 * 0.2 ** 2) <= 1e-4      # the stretched bond alone
+    m = RO.minimise(*_args(case, 0), RC.STRETCH_STEPS, k_rest=RC.STRETCH_K_REST)
+    moved = m["pos"][1, :4] - case["pos"][0, 1, :4].astype(np.float64)
+    assert np.abs(moved + t * axis).max() <= RC.STRETCH_TOL, np.abs(moved + t * axis).max()
+    assert m["terms_final"][1] < 1e-6 and m["terms_final"][3] == 0
+    # why the case does not run with the default k_rest = 10: there the minimum itself deforms the residue.  5000 iterations leave
+    # the energy falling by less than 1e-9 per iteration, and the intra term stands four orders above the issue's 1e-6
+    m = RO.minimise(*_args(case, 0), 5000)
+    assert m["energy_trace"][-2] - m["energy_trace"][-1] < 1e-9 and m["grad_max"] < 1e-2, (m["energy_trace"][-3:], m["grad_max"])
+    assert m["terms_final"][1] > 1e-2, m["terms_final"]
+
+    case = RC.lone_residue()
+    m = RO.minimise(*_args(case, 0), 5)
+    assert not m["energy_trace"].any() and m["iterations"] == 0 and not m["accepted"].any()
+    assert np.array_equal(m["pos"], case["pos"][0].astype(np.float64))
+
+
+def test_oracle_replays_decisions_and_runs_in_float32():
+    case = RC.start_case(4102, 17)
+    free = RO.minimise(*_args(case, 0), 12)
+    again = RO.minimise(*_args(case, 0), 12, replay=free["accepted"])
+    assert np.array_equal(free["pos"], again["pos"]) and np.array_equal(free["energy_trace"], again["energy_trace"])
+    flipped = RO.minimise(*_args(case, 0), 12, replay=np.zeros(12, bool))
+    assert np.array_equal(flipped["pos"], case["pos"][0].astype(np.float64)) and (np.diff(flipped["energy_trace"]) == 0).all()
+    low = RO.minimise(*_args(case, 0), 12, replay=free["accepted"], dtype=np.float32)
+    dev = np.abs(low["pos"] - free["pos"]).max()
+    assert 0 < dev < 1e-4, dev
+    a = free["step_size"]
+    for i in range(11):
+        assert a[i + 1] == np.float32(1.2 if free["accepted"][i] else 0.5) * a[i]
+
+
+def test_seeds_of_the_minimiser_cases():
+    """the conditions relax_cases.py states beside REPLAY_SEED, on the free-running float64 oracle"""
+    case = RC.start_case()
+    m = RO.minimise(*_args(case, 0), RC.REPLAY_STEPS, **RC.decision_bounds(case))
+    assert (m["decision_bound"] > 0).all()
+    clear = np.abs(m["delta_e"]) > 10 * m["decision_bound"]
+    assert clear.mean() >= 0.9, clear.mean()
+    before, after = RC.flagged(case, 0, case["pos"][0]), RC.flagged(case, 0, m["pos"])
+    assert before > 0 and after < before, (before, after)
+    assert m["energy_trace"][-1] < m["energy_trace"][0]
