@@ -1110,6 +1110,47 @@ typedef struct {
 } pf_contacts_args;
 int pf_contacts_fwd(const pf_contacts_args* a, pf_stream_t stream);
 
+/* ---- clustering of samples from a pairwise distance matrix (ABI 64, added entry points) ---------------------------------------------
+ * pf_cluster_fwd: the samples of each group clustered on a [B,B] distance matrix (what the pairwise_* functions return: symmetric,
+ * NaN across groups); the conventions and the tie rules are listed in csrc/clustering.hip.  index [B] lists the batch indices sorted
+ * by group and ascending inside a group, offsets [G+1] the groups' ranges in it; a sample's position is its rank inside its group.
+ * For positions a < b only dist[index[a], index[b]] is read, never the mirrored entry or the diagonal; NaN counts as +inf and is
+ * never within a cutoff (a cutoff of +inf is taken as FLT_MAX).
+ *   method 0  gromos (Daura et al. 1999): repeatedly the active sample with the most active neighbours (d <= cutoff, itself included;
+ *             of equal counts the smallest position) and those neighbours leave as the next cluster; the representative is that centre;
+ *   method 1, 2, 3  single, complete, average linkage: the pair of clusters with the smallest linkage distance (of equal distances the
+ *             smallest (i, j), a cluster named by its smallest position) merges while that distance is <= cutoff; average is
+ *             (n_i d_ik + n_j d_jk) / (n_i + n_j) in fp64.  Labels by size descending, then smallest position; the representative is
+ *             the medoid (smallest fp64 sum of distances to the other members, summed in ascending position; ties: smallest position).
+ *   label, cluster_size, representative, n_neighbours [B] at the sample's batch index; representative and best are batch indices;
+ *   best [B] (with score): the member of the own cluster with the lowest score, NaN last, ties to the smallest position;
+ *   n_neighbours: the neighbour count over the whole group, itself included (every method);  n_clusters [G].
+ * work: G x pf_cluster_work_bytes(n_max, method) bytes (the linkages' working matrix; 0 for gromos, work may then be null), no
+ * initialisation needed.  n_max: an upper bound on the group sizes, which sizes the LDS and the scratch stride; a group above it, or
+ * offsets / index entries out of range, give n_clusters 0 for that group and nothing else written.  One launch, one workgroup per
+ * group, integer outputs with one writer each: bit-identical from run to run and independent of the other groups.
+ * n_max > PF_CLUSTER_MAX_N -> PF_E_TOOLARGE. */
+#define PF_CLUSTER_MAX_N 1024
+#define PF_CLUSTER_GROMOS 0
+#define PF_CLUSTER_SINGLE 1
+#define PF_CLUSTER_COMPLETE 2
+#define PF_CLUSTER_AVERAGE 3
+typedef struct {
+    const float* dist;                                              /* [B,B] */
+    const int* index;                                               /* [B] */
+    const int* offsets;                                             /* [G+1] */
+    const float* score;                                             /* [B] optional */
+    void* work;                                                     /* G x pf_cluster_work_bytes(n_max, method) bytes */
+    int* label; int* cluster_size; int* representative;             /* [B] */
+    int* best;                                                      /* [B], with score */
+    int* n_neighbours;                                              /* [B] */
+    int* n_clusters;                                                /* [G] */
+    int B, G, n_max, method;
+    float cutoff;                                                   /* >= 0 */
+} pf_cluster_args;
+int pf_cluster_fwd(const pf_cluster_args* a, pf_stream_t stream);
+int pf_cluster_work_bytes(int n_max, int method);  /* scratch bytes per group (-1 for n_max outside [1, PF_CLUSTER_MAX_N] or a bad method) */
+
 /* ---- empirical interface energy (ABI 64, added entry point) -----------------------------------------------------------------------
  * pf_interface_energy_fwd: the functional form of AutoDock Vina's scoring function (Trott & Olson, J. Comput. Chem. 2010) over the
  * heavy atoms of a batch of structures, between atoms of residues whose group bytes differ; the conventions are listed in

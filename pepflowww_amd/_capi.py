@@ -239,6 +239,12 @@ class ContactsArgs(C.Structure):
                 ("n_atoms_y", _i), ("slot_mask", _i), ("contact_cutoff", C.c_float), ("interface_cutoff", C.c_float)]
 
 
+class ClusterArgs(C.Structure):
+    _fields_ = [("dist", _fp), ("index", _fp), ("offsets", _fp), ("score", _fp), ("work", _fp), ("label", _fp), ("cluster_size", _fp),
+                ("representative", _fp), ("best", _fp), ("n_neighbours", _fp), ("n_clusters", _fp), ("B", _i), ("G", _i), ("n_max", _i),
+                ("method", _i), ("cutoff", C.c_float)]
+
+
 class InterfaceEnergyArgs(C.Structure):
     _fields_ = [("pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("group", _fp), ("query", _fp), ("radius", _fp), ("types", _fp),
                 ("work", _fp), ("terms_atom", _fp), ("terms_residue", _fp), ("energy_residue", _fp), ("pairs_atom", _fp),
@@ -343,6 +349,8 @@ _SIGNATURES = {
     "pf_sidechain_compare_fwd": ([C.POINTER(SidechainCompareArgs), _fp], _i),
     "pf_lddt_fwd": ([C.POINTER(LddtArgs), _fp], _i),
     "pf_contacts_fwd": ([C.POINTER(ContactsArgs), _fp], _i),
+    "pf_cluster_fwd": ([C.POINTER(ClusterArgs), _fp], _i),
+    "pf_cluster_work_bytes": ([_i, _i], _i),
     "pf_interface_energy_fwd": ([C.POINTER(InterfaceEnergyArgs), _fp], _i),
     "pf_relax_energy_fwd": ([C.POINTER(RelaxArgs), _fp], _i),
     "pf_relax_fwd": ([C.POINTER(RelaxArgs), _fp], _i),

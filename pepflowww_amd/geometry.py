@@ -1,5 +1,5 @@
 """Evaluation geometry on the device: thin wrappers that check their arguments, bind device pointers into one argument struct and
-launch one HIP entry point each (the kernels and their conventions are described in csrc/*.hip; DESIGN.md 3.8-3.16).
+launch one HIP entry point each (the kernels and their conventions are described in csrc/*.hip; DESIGN.md 3.8-3.18).
 
 Input families, one binding path each:
   pair work lists   point sets x [Bx,N,3] / y [By,N,3] with masks and `pairs` [P,2] -- `_pair_inputs`: superpose (and align, batch_align,
@@ -9,6 +9,10 @@ Input families, one binding path each:
   both at once      two heavy-atom structure sets and a work list -- `_structure_pairs`: lddt (pf_lddt_fwd, the values of OpenFold's
                     lddt / lddt_ca, openfold/utils/loss.py:382-458) and interface_contacts (pf_contacts_fwd), which dockq combines
                     with `superpose` into Fnat, iRMSD, LRMSD and DockQ.
+  distance matrices a [B,B] device matrix of one of the pairwise_* functions and host group labels -- `cluster` (pf_cluster_fwd): gromos
+                    and single / complete / average linkage clusters of the samples of each group, their representatives and the
+                    best-scored member of each.  The linkages are checked against scipy's fcluster(criterion="distance"), as
+                    partitions only; gromos follows the publication (Daura et al. 1999) and is not checked against GROMACS.
 `_bind_in` / `_bind_out` fill the struct, `_as_bool` turns the byte outputs into bool, `_table` keeps the per-device constant tables.
 
 Deviation from the reference: `batch_align` selects each sample's masked atoms on their own.  The reference's
@@ -296,6 +300,75 @@ def pairwise_tm_align(x, mask, groups=None):
     pairs = _within_groups(B, groups)
     max_len = int(torch.as_tensor(mask).bool().sum(1).max()) if B else 0
     return _mirrored(B, pairs, x.device, (tm_align(x, x, mask, mask, pairs, max_len=max_len)["tm"], 1.0))[0]
+
+
+CLUSTER_MAX_N = 1024        # PF_CLUSTER_MAX_N: the most samples one group may hold
+CLUSTER_METHODS = ("gromos", "single", "complete", "average")      # pf_cluster_args.method 0..3
+
+
+def cluster(dist, cutoff, groups=None, method="gromos", score=None):
+    """pf_cluster_fwd: the samples of each group clustered on the distance matrix `dist` [B,B] (a device tensor; what the pairwise_*
+    functions return: symmetric, NaN across groups), one launch, one workgroup per group, nothing read back and no synchronisation.
+
+    groups [B]: any integer labels on the host, as `group_pairs` takes (None: one group), at most CLUSTER_MAX_N samples each.  A
+    sample's position is its rank inside its group.  For positions a < b only dist[a, b] right of the diagonal is read; NaN counts as
+    +inf and is never within `cutoff` (>= 0; +inf is taken as the largest float).
+    method: "gromos" -- Daura et al. 1999: the active sample with the most active neighbours (d <= cutoff, itself included; of equal
+    counts the smallest position) leaves with them as the next cluster, labels in that order, the representative is that centre;
+    "single" / "complete" / "average" -- agglomerative: the pair of clusters with the smallest linkage distance (of equal distances
+    the smallest (i, j), a cluster named by its smallest position) merges while that distance is <= cutoff, i.e. the dendrogram cut
+    at height cutoff; labels by size descending, then smallest position; the representative is the medoid (smallest fp64 sum of
+    distances to the other members, of equal sums the smallest position).
+    The linkages are checked against scipy's fcluster(criterion="distance"), as partitions only; gromos follows the publication and
+    is not checked against GROMACS.
+    score [B] (optional, lower is better): adds `best`.
+
+    -> dict of device tensors: label [B] int32 (the cluster number inside the own group, 0 first), cluster_size [B], representative
+    [B] (a batch index), best [B] (with score: the batch index of the own cluster's member with the lowest score, NaN last, of equal
+    scores the smallest position), n_neighbours [B] (samples of the group within cutoff, itself included; every method),
+    n_clusters [G]; index [B], offsets [G+1] int32 (the batch indices sorted by group, and the groups' ranges in it),
+    group_labels [G] (sorted), group_of [B] (an index into group_labels)."""
+    if not isinstance(dist, torch.Tensor) or dist.dim() != 2 or dist.shape[0] != dist.shape[1]:
+        raise ValueError(f"dist must be a [B,B] tensor, got {tuple(getattr(dist, 'shape', ()))}")
+    B = dist.shape[0]
+    if method not in CLUSTER_METHODS:
+        raise ValueError(f"method must be one of {CLUSTER_METHODS}, got {method!r}")
+    cutoff = float(cutoff)
+    if not cutoff >= 0.0:
+        raise ValueError(f"cutoff must be >= 0, got {cutoff}")
+    if score is not None and (not isinstance(score, torch.Tensor) or tuple(score.shape) != (B,)):
+        raise ValueError(f"score must be [B] = {(B,)}, got {tuple(getattr(score, 'shape', ()))}")
+    g = torch.zeros(B, dtype=torch.int64) if groups is None else torch.as_tensor(groups).reshape(-1).cpu()
+    if g.numel() != B:
+        raise ValueError(f"groups has {g.numel()} labels for {B} samples")
+    labels, inv, counts = torch.unique(g, sorted=True, return_inverse=True, return_counts=True)
+    G, n_max = labels.numel(), int(counts.max()) if B else 0
+    if n_max > CLUSTER_MAX_N:
+        raise ValueError(f"at most {CLUSTER_MAX_N} samples per group, got {n_max}")
+    a = _capi.ClusterArgs()
+    dev = dist.device
+    keep = [_f32(dist, dev), None if score is None else _f32(score, dev)]
+    _bind_in(a, dist=keep[0], score=keep[1])
+    offsets = torch.zeros(G + 1, dtype=torch.int64)
+    offsets[1:] = torch.cumsum(counts, 0)
+    out = {k: torch.empty(B, dtype=torch.int32, device=dev) for k in ("label", "cluster_size", "representative", "n_neighbours")}
+    if score is not None:
+        out["best"] = torch.empty(B, dtype=torch.int32, device=dev)
+    out["n_clusters"] = torch.empty(G, dtype=torch.int32, device=dev)
+    _bind_out(a, out)
+    out["index"] = torch.argsort(inv, stable=True).to(torch.int32).to(dev)
+    out["offsets"] = offsets.to(torch.int32).to(dev)
+    _bind_in(a, index=out["index"], offsets=out["offsets"])
+    a.B, a.G, a.n_max, a.method, a.cutoff = B, G, n_max, CLUSTER_METHODS.index(method), cutoff
+    if B:
+        lib = _capi.load()
+        work = G * lib.pf_cluster_work_bytes(n_max, a.method)
+        if work:
+            keep.append(torch.empty(work, dtype=torch.uint8, device=dev))
+            a.work = keep[-1].data_ptr()
+        _capi.check(lib.pf_cluster_fwd(C.byref(a), _capi.stream_ptr()), "pf_cluster_fwd")
+    out["group_labels"], out["group_of"] = labels.to(dev), inv.to(dev)
+    return out
 
 
 DSSP_MAX_N = 512            # PF_DSSP_MAX_N: the longest chain slot pf_dssp_fwd takes

@@ -9,10 +9,13 @@ side-chain packing table, chi1-chi4 errors against the native and the share of r
 (`sidechain_packing`); superposition-free local accuracy, lDDT with the values of OpenFold's lddt / lddt_ca
 (openfold/utils/loss.py:382-458), over the peptide and across the interface (`local_accuracy`); docking quality, Fnat, iRMSD, LRMSD and
 DockQ (`docking_quality`); an empirical peptide-receptor interface energy, the functional form of AutoDock Vina's scoring function
-written from the publication and not checked against that program (`binding_energy`).
+written from the publication and not checked against that program (`binding_energy`); structural clusters of the samples of each
+complex, their representatives and the best-scored member of each (`cluster_samples`: gromos clustering after Daura et al. 1999, which
+follows the publication and is not checked against GROMACS, and single / complete / average linkage cut at a height, checked against
+scipy's fcluster(criterion="distance") as partitions only).
 
 Every per-residue, per-point and per-atom-pair operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd /
-pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_relax_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
+pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_relax_fwd / pf_cluster_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
@@ -202,6 +205,50 @@ def structure_scores(final, batch, groups=None, novelty_tm=0.5, novelty_ident=0.
     div_tm = 1.0 - _group_sum(ptm, gidx, G) / _group_sum(torch.ones_like(gidx), gidx, G)
     return {"tm": tm, "tm_pooled": tm.double().mean(), "novel": novel, "novelty": novelty, "diversity_tm": div_tm,
             "group_labels": glab}
+
+
+CLUSTER_METRICS = ("rmsd", "pose_rmsd", "tm", "tmalign")
+# this package's own default cutoffs, not taken from a publication or a program: 2.0 A for the two RMSDs, 0.5 for the two TM distances
+CLUSTER_CUTOFFS = {"rmsd": 2.0, "pose_rmsd": 2.0, "tm": 0.5, "tmalign": 0.5}
+
+
+def cluster_samples(final, batch, groups=None, metric="rmsd", cutoff=None, method="gromos", score=None):
+    """Structural clusters of the samples of each complex, from `sample()` output to cluster labels without leaving the device.
+    final / batch / groups as in `evaluate_samples` (only final["trans"] and batch["generate_mask"] are read): the points are the
+    sampled CAs over the generated residues.
+
+    metric: the distance between two samples of one group --
+      "rmsd"       CA RMSD after the optimal proper superposition (geometry.pairwise_superpose_rmsd);
+      "pose_rmsd"  CA RMSD without superposition, in the receptor's frame (superpose's rmsd_plain): what docking pose clustering uses;
+      "tm"         1 - TM-score with the correspondence fixed (geometry.pairwise_tm_score);
+      "tmalign"    1 - TM-align's score (geometry.pairwise_tm_align).
+    cutoff: None takes CLUSTER_CUTOFFS[metric] -- 2.0 A for the two RMSDs, 0.5 for the two TM distances; these defaults are this
+    package's own choices.  method: one of geometry.CLUSTER_METHODS; "gromos" follows Daura et al. 1999 and is not checked against
+    GROMACS, the linkages are checked against scipy's fcluster(criterion="distance") as partitions only.
+    score [B] (optional, lower is better; `binding_energy`'s total or a relaxed energy): adds `best`.
+
+    -> the dict of `geometry.cluster` (label, cluster_size, representative, best, n_neighbours, n_clusters, index, offsets,
+    group_labels, group_of) and dist [B,B] (NaN across groups), cluster_diversity [G] float64 = n_clusters / the group's size."""
+    if metric not in CLUSTER_METRICS:
+        raise ValueError(f"metric must be one of {CLUSTER_METRICS}, got {metric!r}")
+    labels = _check_groups(batch["generate_mask"], groups)
+    dev = _device(batch["generate_mask"], final["trans"])
+    x = final["trans"].to(dev)
+    gen = batch["generate_mask"].to(dev).bool()
+    B = x.shape[0]
+    if metric == "rmsd":
+        dist = geometry.pairwise_superpose_rmsd(x, gen, groups=labels)
+    elif metric == "pose_rmsd":
+        pairs = geometry._within_groups(B, labels)
+        dist = geometry._mirrored(B, pairs, dev, (superpose(x, x, gen, gen, pairs)["rmsd_plain"], 0.0))[0]
+    elif metric == "tm":
+        dist = 1.0 - geometry.pairwise_tm_score(x, gen, groups=labels)
+    else:
+        dist = 1.0 - geometry.pairwise_tm_align(x, gen, groups=labels)
+    out = geometry.cluster(dist, CLUSTER_CUTOFFS[metric] if cutoff is None else cutoff, groups=labels, method=method, score=score)
+    out["dist"] = dist
+    out["cluster_diversity"] = out["n_clusters"].double() / (out["offsets"][1:] - out["offsets"][:-1]).double()
+    return out
 
 
 def secondary_structure(final, batch, backbone="full_atom"):
