@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PF_ABI_VERSION 64
+#define PF_ABI_VERSION 65
 #define PF_ATT_VROWS 164             /* rows of a head's transposed value block: 128 channels + 12 points x 3 */
 /* att_vt (f16 mode, ABI 53): a head's transposed values [PF_ATT_VROWS rows][keys] in the FRAGMENT ORDER of the score kernel's second
  * product -- block (tile n, 32-key step) = 512 f16 = the eight operand slots of each of its 64 lanes: row c sits in tile n = c & 7 as
@@ -454,6 +454,11 @@ typedef struct {
     float* mres; float* ctx;   /* [B*L] residue mask (CA present), context mask (CA present & !generate) */
     int B, L;
     int sample_structure, sample_sequence;   /* cfg.interpolant flags (flow_model.py:86-87) */
+    /* (ABI 65) residues per sample of the CALLER's batch when the launch runs at another length (0 = L): the dihedral mask
+     * structure_mask & roll(+1) & roll(-1) of node.py:86-93 wraps over the caller's residue axis -- residue 0's wrapped neighbour is
+     * the caller's residue L0 - 1 (caller padding = False when L0 - 1 >= L, a batch cut to a length bucket), residue L0 - 1's is
+     * residue 0; rows L0 .. L - 1 of a launch padded up are padding. */
+    int L0;
 } pf_node_feat_args;
 int pf_node_features_fwd(const pf_node_feat_args* a, pf_stream_t stream);
 

@@ -391,11 +391,13 @@ def backbone_dihedrals(pos, chain_nb, res_nb, mask):
     return torch.stack([omega, phi, psi], dim=-1) * m, m
 
 
-def node_embedder(sd, aa, res_nb, chain_nb, pos, mask_atoms, context_mask):
-    """NodeEmbedder.forward, node.py:35-104 (structure_mask = sequence_mask = context_mask)."""
+def node_embedder(sd, aa, res_nb, chain_nb, pos, mask_atoms, structure_mask=None, sequence_mask=None):
+    """NodeEmbedder.forward, node.py:35-104.  structure_mask / sequence_mask: the context mask or None (node.py:54,76,84;
+    flow_model.py:86-87 passes the same mask for both, or None where cfg.interpolant.sample_structure / sample_sequence is off)."""
     B, L = aa.shape
     mres = mask_atoms[:, :, BB_CA]
-    aa = torch.where(context_mask, aa, torch.full_like(aa, AA_UNK))
+    if sequence_mask is not None:
+        aa = torch.where(sequence_mask, aa, torch.full_like(aa, AA_UNK))
     aa_feat = sd["node_embedder.aatype_embed.weight"][aa]
     R = construct_3d_basis(pos[:, :, BB_CA], pos[:, :, BB_C], pos[:, :, BB_N])
     t = pos[:, :, BB_CA]
@@ -403,12 +405,14 @@ def node_embedder(sd, aa, res_nb, chain_nb, pos, mask_atoms, context_mask):
     crd = torch.where(mask_atoms[..., None], crd, torch.zeros_like(crd))
     place = F.one_hot(aa, 22).to(crd.dtype)                                # [B,L,22]
     crd_feat = (place[:, :, :, None, None] * crd[:, :, None]).reshape(B, L, 22 * 15 * 3)
-    crd_feat = crd_feat * context_mask[:, :, None]
+    if structure_mask is not None:
+        crd_feat = crd_feat * structure_mask[:, :, None]
     dih, dmask = backbone_dihedrals(pos, chain_nb, res_nb, mres)
     dfeat = angular_encoding(dih[..., None], 3) * dmask[..., None]
     dfeat = dfeat.reshape(B, L, -1)
-    keep = context_mask & torch.roll(context_mask, 1, 1) & torch.roll(context_mask, -1, 1)
-    dfeat = dfeat * keep[:, :, None]
+    if structure_mask is not None:
+        keep = structure_mask & torch.roll(structure_mask, 1, 1) & torch.roll(structure_mask, -1, 1)
+        dfeat = dfeat * keep[:, :, None]
     h = torch.cat([aa_feat, crd_feat, dfeat], dim=-1)
     for i in (0, 2, 4):
         h = torch.relu(lin(sd, f"node_embedder.mlp.{i}", h))
@@ -416,13 +420,14 @@ def node_embedder(sd, aa, res_nb, chain_nb, pos, mask_atoms, context_mask):
     return h * mres[:, :, None]
 
 
-def edge_embedder(sd, aa, res_nb, chain_nb, pos, mask_atoms, context_mask):
-    """EdgeEmbedder.forward, edge.py:39-111."""
+def edge_embedder(sd, aa, res_nb, chain_nb, pos, mask_atoms, structure_mask=None, sequence_mask=None):
+    """EdgeEmbedder.forward, edge.py:39-111.  structure_mask / sequence_mask: the context mask or None (edge.py:62,65,88,95)."""
     B, L = aa.shape
     mres = mask_atoms[:, :, BB_CA]
     mpair = mres[:, :, None] * mres[:, None, :]
-    spair = (context_mask[:, :, None] * context_mask[:, None, :])
-    aa = torch.where(context_mask, aa, torch.full_like(aa, AA_UNK))
+    spair = (structure_mask[:, :, None] * structure_mask[:, None, :]) if structure_mask is not None else None
+    if sequence_mask is not None:
+        aa = torch.where(sequence_mask, aa, torch.full_like(aa, AA_UNK))
     aap = aa[:, :, None] * 22 + aa[:, None, :]
     f_aap = sd["edge_embedder.aa_pair_embed.weight"][aap]
     same = (chain_nb[:, :, None] == chain_nb[:, None, :])
@@ -435,12 +440,15 @@ def edge_embedder(sd, aa, res_nb, chain_nb, pos, mask_atoms, context_mask):
     f_d = g * mat
     for i in (0, 2):
         f_d = torch.relu(lin(sd, f"edge_embedder.distance_embed.{i}", f_d))
-    f_d = f_d * spair[..., None]
+    if spair is not None:
+        f_d = f_d * spair[..., None]
     N_, CA, C_ = pos[:, :, BB_N], pos[:, :, BB_CA], pos[:, :, BB_C]
     ex = lambda v, ax: (v[:, :, None] if ax == 0 else v[:, None, :]).expand(B, L, L, 3)
     phi = dihedral(ex(C_, 0), ex(N_, 1), ex(CA, 1), ex(C_, 1))
     psi = dihedral(ex(N_, 0), ex(CA, 0), ex(C_, 0), ex(N_, 1))
-    f_dh = angular_encoding(torch.stack([phi, psi], -1), 3) * spair[..., None]
+    f_dh = angular_encoding(torch.stack([phi, psi], -1), 3)
+    if spair is not None:
+        f_dh = f_dh * spair[..., None]
     h = torch.cat([f_aap, f_rel, f_d, f_dh], dim=-1)
     h = torch.relu(lin(sd, "edge_embedder.out_mlp.0", h))
     h = torch.relu(lin(sd, "edge_embedder.out_mlp.2", h))
@@ -448,14 +456,15 @@ def edge_embedder(sd, aa, res_nb, chain_nb, pos, mask_atoms, context_mask):
     return h * mpair[..., None]
 
 
-def encode(sd, batch):
-    """FlowModel.encode, flow_model.py:75-93 (sample_structure = sample_sequence = True)."""
+def encode(sd, batch, sample_structure=True, sample_sequence=True):
+    """FlowModel.encode, flow_model.py:75-93; sample_structure / sample_sequence: cfg.interpolant's switches (flow_model.py:86-87)."""
     pos = batch["pos_heavyatom"]
     R1 = construct_3d_basis(pos[:, :, BB_CA], pos[:, :, BB_C], pos[:, :, BB_N])
     x1 = pos[:, :, BB_CA]
     ctx = batch["mask_heavyatom"][:, :, BB_CA] & ~batch["generate_mask"]
-    args = (batch["aa"], batch["res_nb"], batch["chain_nb"], pos, batch["mask_heavyatom"], ctx)
-    return R1, x1, batch["torsion_angle"], batch["aa"], node_embedder(sd, *args), edge_embedder(sd, *args)
+    args = (batch["aa"], batch["res_nb"], batch["chain_nb"], pos, batch["mask_heavyatom"])
+    masks = dict(structure_mask=ctx if sample_structure else None, sequence_mask=ctx if sample_sequence else None)
+    return R1, x1, batch["torsion_angle"], batch["aa"], node_embedder(sd, *args, **masks), edge_embedder(sd, *args, **masks)
 
 
 # ----------------------------------------------------------------------------

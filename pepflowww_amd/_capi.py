@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (PF_LIB_PATH: another build of the same library -- same-box A/B runs of kernel variants, tools/dev)
 LIB_PATH = os.environ.get("PF_LIB_PATH") or os.path.join(_HERE, "lib", "libpepflow_hip.so")
-ABI_VERSION = 64
+ABI_VERSION = 65
 
 _fp = C.c_void_p
 _i = C.c_int
@@ -136,7 +136,7 @@ class BackboneAtomsArgs(C.Structure):
 class NodeFeatArgs(C.Structure):
     _fields_ = [("aa", _fp), ("res_nb", _fp), ("chain_nb", _fp), ("pos", _fp), ("mask_atoms", _fp), ("gen_mask", _fp),
                 ("aa_table", _fp), ("freq3", _fp), ("feat", _fp), ("rot1", _fp), ("trans1", _fp), ("mres", _fp),
-                ("ctx", _fp), ("B", _i), ("L", _i), ("sample_structure", _i), ("sample_sequence", _i)]
+                ("ctx", _fp), ("B", _i), ("L", _i), ("sample_structure", _i), ("sample_sequence", _i), ("L0", _i)]
 
 
 class EdgeFeatArgs(C.Structure):

@@ -144,7 +144,7 @@ class BucketedSampler:
             shapes[(len(idx), Lk)] = slot + 1
             eng = model.ga_encoder.engine(len(idx), Lk, dev, slot=slot)
             stamp("engine")
-            R1, x1, ang1, seq1, node, edge = model.encode(sb, edge_out=eng.edge_buffer())
+            R1, x1, ang1, seq1, node, edge = model.encode(sb, edge_out=eng.edge_buffer(), caller_len=L0)
             stamp("encode")
             eng.bind_context(node, edge, sb["res_mask"])
             stamp("bind")

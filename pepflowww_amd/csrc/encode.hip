@@ -12,6 +12,11 @@
 // rounding noise.  To reproduce the reference's value the cross product and the dot product follow
 // ATen's CPU op sequence exactly: cross_k = fma(a_i, b_j, -(a_j*b_i)), dot = (m0 + m1) + m2
 // (verified bitwise against torch 2.10 CPU, see NOTES.md 3.6).  Compiled with -ffp-contract=off.
+// Where a cross product is exactly zero (three collinear points) the cosine is NaN: torch.clamp keeps it and nan_to_num returns 0,
+// whatever the sign of the triple product -- dihedral4 returns 0 there too (golden F16, case `collinear`).
+//
+// The dihedral mask of NodeEmbedder (structure_mask & roll(+1) & roll(-1), node.py:86-93) wraps over the caller's residue axis:
+// pf_node_feat_args.L0 carries that length when the launch runs at another one (sample()'s padding to 16, a length bucket).
 #include <type_traits>
 #include "common.h"
 #include "../../include/pepflow_hip.h"
@@ -39,6 +44,7 @@ __device__ __forceinline__ float dihedral4(V3 p0, V3 p1, V3 p2, V3 p3) {   // ge
     const float t = dot_seq(cross_aten(v1, v2), v0);
     const float sg = t > 0.f ? 1.f : (t < 0.f ? -1.f : 0.f);
     float c = dot_seq(n1, n2);
+    if (c != c) return 0.f;                                     // torch.clamp keeps a NaN cosine (fminf / fmaxf drop it), nan_to_num makes it 0
     c = fminf(fmaxf(c, -0.999999f), 0.999999f);
     const float d = sg * acosf(c);
     return (d != d) ? 0.f : d;                                  // nan_to_num
@@ -117,9 +123,12 @@ __global__ __launch_bounds__(256) void node_features_kernel(pf_node_feat_args a)
         }
     }
     float dkeep = 1.f;
-    if (a.sample_structure) {       // structure_mask & roll(+1) & roll(-1), with wrap-around (node.py:86-93)
-        const int prev = b * L + (l == 0 ? L - 1 : l - 1), next = b * L + (l == L - 1 ? 0 : l + 1);
-        dkeep = ctx * ctx_of(prev) * ctx_of(next);
+    if (a.sample_structure) {       // structure_mask & roll(+1) & roll(-1) (node.py:86-93): the roll wraps over the CALLER's L0 residues,
+        // whatever length the launch has (padded up: rows L0.. are padding; cut to a bucket: rows L.. of the caller are padding = False)
+        const int L0 = a.L0 > 0 ? a.L0 : L;
+        const float pctx = l == 0 ? (L0 - 1 < L ? ctx_of(b * L + L0 - 1) : 0.f) : ctx_of(row - 1);
+        const float nctx = l == L0 - 1 ? ctx_of(b * L) : (l + 1 < L ? ctx_of(row + 1) : 0.f);
+        dkeep = ctx * pctx * nctx;
     }
 
     for (int c = threadIdx.x; c < 1168; c += 256) {
@@ -355,7 +364,7 @@ __global__ __launch_bounds__(256) void edge_features_kernel(pf_edge_feat_args a,
 
 extern "C" int pf_node_features_fwd(const pf_node_feat_args* a, pf_stream_t stream) {
     if (!a || !a->aa || !a->res_nb || !a->chain_nb || !a->pos || !a->mask_atoms || !a->gen_mask || !a->aa_table ||
-        !a->freq3 || !a->feat || !a->rot1 || !a->trans1 || !a->mres || !a->ctx || a->B <= 0 || a->L <= 0)
+        !a->freq3 || !a->feat || !a->rot1 || !a->trans1 || !a->mres || !a->ctx || a->B <= 0 || a->L <= 0 || a->L0 < 0)
         return PF_E_BADARG;
     hipLaunchKernelGGL(node_features_kernel, dim3((unsigned)(a->B * a->L)), dim3(256), 0, (hipStream_t)stream, *a);
     PF_CHECK_LAUNCH();

@@ -78,8 +78,10 @@ def embedder_forward(which, module, aa, res_nb, chain_nb, pos_atoms, mask_atoms,
     return out[4] if which == "node" else out[5]
 
 
-def encode(model, batch, save=None, edge_out=None, parts=("node", "edge")):
-    """save: optional dict that receives every intermediate the encoder backward needs (training path).
+def encode(model, batch, save=None, edge_out=None, parts=("node", "edge"), caller_len=None):
+    """caller_len: residues per sample of the CALLER's batch when `batch` is that batch padded up or cut to another length (sample()'s
+    padding to 16, a length bucket): NodeEmbedder's dihedral mask wraps over the caller's residue axis (pf_node_feat_args.L0).
+    save: optional dict that receives every intermediate the encoder backward needs (training path).
     edge_out: optional fp32 [B,L,L,64] buffer the pair embedding is written to (FlowModel.sample hands the denoise engine's own
     input buffer, so that the engine's launch plan / captured graphs keep their pointers from one call to the next).
     parts: which embedder runs (a stand-alone NodeEmbedder / EdgeEmbedder call, embedder_forward; the other output is None)."""
@@ -88,6 +90,8 @@ def encode(model, batch, save=None, edge_out=None, parts=("node", "edge")):
     _capi.dptr(aa.contiguous(), torch.int64, "batch['aa']")
     dev = aa.device
     B, L = aa.shape
+    if caller_len is not None and (int(caller_len) != caller_len or caller_len < 1):
+        raise ValueError(f"caller_len = {caller_len!r}: the caller's residues per sample, a positive integer (or None: the batch is the caller's)")
     rows = B * L
     aa_c = aa.contiguous()
     res_nb, chain_nb = batch["res_nb"].to(torch.int64).contiguous(), batch["chain_nb"].to(torch.int64).contiguous()
@@ -110,7 +114,7 @@ def encode(model, batch, save=None, edge_out=None, parts=("node", "edge")):
         aa_table, freq_n = torch.zeros(22, 128, device=dev), _f32(ee.dihedral_embed.freq_bands)
     na.aa_table, na.freq3 = aa_table.data_ptr(), freq_n.data_ptr()
     na.feat, na.rot1, na.trans1, na.mres, na.ctx = feat.data_ptr(), rot1.data_ptr(), trans1.data_ptr(), mres.data_ptr(), ctx.data_ptr()
-    na.B, na.L = B, L
+    na.B, na.L, na.L0 = B, L, int(caller_len or 0)
     na.sample_structure, na.sample_sequence = int(bool(model.sample_structure)), int(bool(model.sample_sequence))
     _capi.check(lib.pf_node_features_fwd(C.byref(na), _capi.stream_ptr()), "pf_node_features_fwd")
 

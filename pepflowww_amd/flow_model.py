@@ -94,9 +94,10 @@ class FlowModel(nn.Module):
         assert self.K == 20 and float(self.k) == 5.0, "sampler kernels are specialised to learn_angle.yaml:30-31"
 
     # ---- flow_model.py:75-93 ----
-    def encode(self, batch, edge_out=None):
+    def encode(self, batch, edge_out=None, caller_len=None):
+        """caller_len: see featurize.encode (set by sample() when it encodes the caller's batch at another length)."""
         _capi.dptr(batch["pos_heavyatom"].contiguous(), name="batch['pos_heavyatom']")
-        return featurize.encode(self, batch, edge_out=edge_out)
+        return featurize.encode(self, batch, edge_out=edge_out, caller_len=caller_len)
 
     # ---- flow_model.py:111-227 ----
     def forward(self, batch, *, noise=None, seed=None, first_sample=0, return_state=False):
@@ -222,7 +223,7 @@ class FlowModel(nn.Module):
         # (GAEncoder.engine / DenoiseEngine.sampler): a second call at a shape seen before only encodes, binds and replays.
         eng = self.ga_encoder.engine(B, L, dev)
         stamp("engine")
-        R1, x1, ang1, seq1, node, edge = self.encode(batch, edge_out=eng.edge_buffer())
+        R1, x1, ang1, seq1, node, edge = self.encode(batch, edge_out=eng.edge_buffer(), caller_len=L0)
         stamp("encode")
         eng.bind_context(node, edge, batch["res_mask"])
         stamp("bind")

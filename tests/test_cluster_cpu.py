@@ -28,7 +28,7 @@ def test_header_bound_and_insertion_points():
     text = open(HEADER).read()
     assert "#define PF_CLUSTER_MAX_N 1024" in text and geometry.CLUSTER_MAX_N == 1024
     assert geometry.CLUSTER_METHODS == ("gromos", "single", "complete", "average")
-    assert "#define PF_ABI_VERSION 64" in text and _capi.ABI_VERSION == 64
+    assert "#define PF_ABI_VERSION 65" in text and _capi.ABI_VERSION == 65
     assert text.index("} pf_contacts_args;") < text.index("} pf_cluster_args;") < text.index("} pf_interface_energy_args;")
     assert build.SOURCES.index("clustering.hip") == build.SOURCES.index("contacts.hip") + 1
     syms = _capi.EXPORTED_SYMBOLS
@@ -37,7 +37,7 @@ def test_header_bound_and_insertion_points():
 
 def test_library_exports_the_entry_points():
     lib = _capi.load()
-    assert lib.pf_abi_version() == _capi.ABI_VERSION == 64
+    assert lib.pf_abi_version() == _capi.ABI_VERSION == 65
     assert lib.pf_cluster_fwd(None, None) == -1
     assert lib.pf_cluster_fwd(C.byref(_capi.ClusterArgs()), None) == -1
     assert lib.pf_cluster_work_bytes(1024, 0) == 0

@@ -84,7 +84,7 @@ def test_struct_layout_agrees_with_the_header():
 
 def test_header_keeps_the_abi_version_and_the_order():
     text = open(HEADER).read()
-    assert "#define PF_ABI_VERSION 64" in text and _capi.ABI_VERSION == 64
+    assert "#define PF_ABI_VERSION 65" in text and _capi.ABI_VERSION == 65
     assert text.index("} pf_contacts_args;") < text.index("} pf_interface_energy_args;")
     assert text.index("int pf_contacts_fwd(") < text.index("int pf_interface_energy_fwd(")
     assert "#define PF_INTERFACE_ENERGY_MAX_N 512" in text and geometry.ENERGY_MAX_N == 512
@@ -94,7 +94,7 @@ def test_header_keeps_the_abi_version_and_the_order():
 def test_library_exports_the_entry_point():
     assert "pf_interface_energy_fwd" in _capi.EXPORTED_SYMBOLS
     lib = _capi.load()
-    assert lib.pf_abi_version() == _capi.ABI_VERSION == 64
+    assert lib.pf_abi_version() == _capi.ABI_VERSION == 65
     assert lib.pf_interface_energy_fwd(None, None) == -1
     assert lib.pf_interface_energy_fwd(C.byref(_capi.InterfaceEnergyArgs()), None) == -1
 

@@ -183,7 +183,7 @@ def test_struct_layout_agrees_with_the_header(struct, cls):
 
 def test_header_keeps_the_abi_version_and_the_order():
     text = open(HEADER).read()
-    assert "#define PF_ABI_VERSION 64" in text and _capi.ABI_VERSION == 64
+    assert "#define PF_ABI_VERSION 65" in text and _capi.ABI_VERSION == 65
     assert text.index("} pf_sidechain_compare_args;") < text.index("} pf_lddt_args;") < text.index("} pf_contacts_args;")
     assert "#define PF_LDDT_MAX_N 512" in text and geometry.LDDT_MAX_N == 512
 

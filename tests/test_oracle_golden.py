@@ -96,6 +96,56 @@ def test_encode(f2, seeded_sd):
     close(edge, f2["enc_edge"], atol=2e-5, rtol=1e-4)
 
 
+def test_encode_on_pocket_inputs(golden_dir, seeded_sd):
+    """The restatement's encode() against the reference's on PDB-shaped inputs (golden F16, tests/pocket_cases.py): receptor
+    fragments with PDB numbering, missing atoms, UNK, the peptide in the middle, all four settings of the sample_structure /
+    sample_sequence switches, and two exactly collinear dihedrals -- every stored array, at test_encode's bounds.  Also the check that
+    the cases are well conditioned, and that the generator still builds the recorded inputs and drives the branches it is there for."""
+    import sys
+    sys.path.insert(0, os.path.dirname(__file__))
+    import pocket_cases as P
+    f16 = P.load_f16(golden_dir)
+    compared = set()
+    for case in P.F16_CASES:
+        made, batch = P.model_inputs(P.make(case)), P.f16_batch(f16, case)
+        assert set(made) == set(batch) and all(torch.equal(made[k], batch[k]) for k in batch), case
+        compared |= {f"{case}.batch_{k}" for k in batch}
+        settings = P.SWITCHES if case == "frag19" else P.SWITCHES[:1]
+        for ss, sq in settings:
+            R1, x1, ang1, seq1, node, edge = O.encode(seeded_sd, batch, sample_structure=ss, sample_sequence=sq)
+            tag = "" if (ss, sq) == (True, True) else f"_ss{int(ss)}_sq{int(sq)}"
+            close(R1, f16[f"{case}.R1"], atol=1e-6)
+            close(x1, batch["pos_heavyatom"][:, :, 1], atol=0)
+            close(node, f16[f"{case}.node{tag}"], atol=2e-5, rtol=1e-4)
+            close(edge, f16[f"{case}.edge{tag}"], atol=2e-5, rtol=1e-4)
+            compared |= {f"{case}.R1", f"{case}.node{tag}", f"{case}.edge{tag}"}
+    # the stand-alone embedders with one mask None (recorded as the switch settings they equal in the reference)
+    b = P.f16_batch(f16, "frag19")
+    ctx = b["mask_heavyatom"][:, :, 1] & ~b["generate_mask"]
+    args = (seeded_sd, b["aa"], b["res_nb"], b["chain_nb"], b["pos_heavyatom"], b["mask_heavyatom"])
+    for tag, kw in (("ss0_sq1", dict(structure_mask=None, sequence_mask=ctx)), ("ss1_sq0", dict(structure_mask=ctx, sequence_mask=None))):
+        close(O.node_embedder(*args, **kw), f16[f"frag19.node_{tag}"], atol=2e-5, rtol=1e-4)
+        close(O.edge_embedder(*args, **kw), f16[f"frag19.edge_{tag}"], atol=2e-5, rtol=1e-4)
+    # exactly collinear p0, p1, p2 with a non-zero sign of the triple product: the reference's angle is 0, and so is the oracle's
+    q = f16["collinear.points"]
+    assert torch.equal(q, P.make("collinear")["collinear_points"])
+    u1, sgn = P.dihedral_terms(q[:, 0], q[:, 1], q[:, 2], q[:, 3])
+    assert (u1 == 0).all() and (sgn != 0).all() and (f16["collinear.dihedrals"] == 0).all()
+    assert (O.dihedral(q[:, 0], q[:, 1], q[:, 2], q[:, 3]) == 0).all()
+    compared |= {"collinear.points", "collinear.dihedrals"}
+    assert compared == set(f16), set(f16) ^ compared
+    # what the cases are there for (an edit of a spec must not silently lose a branch)
+    cov = {c: P.coverage(P.make(c)) for c in P.CASES}
+    rows = set().union(*(c["relpos_rows"] for c in cov.values()))
+    steps = set().union(*(c["steps"] for c in cov.values()))
+    assert {0, 64} <= rows and {-1, 0, 1, 2} <= steps and any(s > 32 for s in steps)
+    assert all(c["no_N"] and c["no_C"] and c["no_CA"] and c["unk_context"] for c in cov.values())
+    assert all(c["chains"][0] == 0 and 3 <= len(c["chains"]) <= 4 and c["max_res_nb"] > 1000 and c["min_res_nb"] < 0 for c in cov.values())
+    assert any(c["beyond_clamp"] for c in cov.values()) and any(c["same_number_other_chain"] for c in cov.values())
+    assert 1 in cov["frag19"]["peptide_lengths"] and cov["pad48"]["lengths"] == [48, 37, 0]
+    assert cov["wrap40"]["lengths"][0] == 40 and cov["wrap40"]["context_at_both_ends"][0] and cov["long130"]["lengths"] == [130]
+
+
 def test_ipa_and_edge_transition(f2, seeded_sd):
     mask = _batch(f2)["res_mask"].float()
     out, _ = O.ipa(seeded_sd, "ga_encoder.trunk.ipa_0", f2["s_in"], f2["enc_edge"], f2["R_t"], f2["x_t"], mask)

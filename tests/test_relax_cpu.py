@@ -78,7 +78,7 @@ def test_struct_layout_agrees_with_the_header():
 
 def test_header_keeps_the_abi_version_and_the_order():
     text = open(HEADER).read()
-    assert "#define PF_ABI_VERSION 64" in text and _capi.ABI_VERSION == 64
+    assert "#define PF_ABI_VERSION 65" in text and _capi.ABI_VERSION == 65
     assert text.index("} pf_interface_energy_args;") < text.index("} pf_relax_args;")
     assert text.index("int pf_interface_energy_fwd(") < text.index("int pf_relax_energy_fwd(") < text.index("int pf_relax_fwd(")
     assert "#define PF_RELAX_MAX_N 512" in text and geometry.RELAX_MAX_N == 512
@@ -90,7 +90,7 @@ def test_header_keeps_the_abi_version_and_the_order():
 
 def test_library_exports_the_entry_points():
     lib = _capi.load()
-    assert lib.pf_abi_version() == _capi.ABI_VERSION == 64
+    assert lib.pf_abi_version() == _capi.ABI_VERSION == 65
     for f in (lib.pf_relax_energy_fwd, lib.pf_relax_fwd):
         assert f(None, None) == -1
         assert f(C.byref(_capi.RelaxArgs()), None) == -1

@@ -216,7 +216,7 @@ def test_wrapper_argument_checks():
 
 def test_c_abi_bounds():
     lib = _capi.load()
-    assert lib.pf_abi_version() == _capi.ABI_VERSION == 64
+    assert lib.pf_abi_version() == _capi.ABI_VERSION == 65
     buf = (C.c_char * 64)()
 
     def filled(cls, optional, **kw):

@@ -160,9 +160,9 @@ def test_wrapper_argument_checks():
 
 
 def test_c_abi_bounds():
-    assert _capi.ABI_VERSION == 64
+    assert _capi.ABI_VERSION == 65
     lib = _capi.load()
-    assert lib.pf_abi_version() == 64
+    assert lib.pf_abi_version() == 65
     a = _capi.ViolationsArgs()
     assert lib.pf_violations_fwd(C.byref(a), None) == -1
     assert lib.pf_violations_fwd(None, None) == -1
