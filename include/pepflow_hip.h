@@ -1156,6 +1156,61 @@ typedef struct {
 int pf_cluster_fwd(const pf_cluster_args* a, pf_stream_t stream);
 int pf_cluster_work_bytes(int n_max, int method);  /* scratch bytes per group (-1 for n_max outside [1, PF_CLUSTER_MAX_N] or a bad method) */
 
+/* ---- rotamer side-chain packing (ABI 65, added entry points) -----------------------------------------------------------------------
+ * pf_pack_sidechains_fwd: every rotamer of a discrete table built on the backbone of each movable residue, scored against the fixed
+ * environment and against each other with the pair function of pf_interface_energy_fwd, and one chosen per residue by iterated
+ * conditional modes; the conventions are listed in csrc/packing.hip.  It is NOT SCWRL4 and NOT Rosetta's packer (no Dunbrack library,
+ * no hydrogens, no fitted parameter; a local search): it takes their place in role only.  Inputs as pf_relax_fwd; a movable residue
+ * of a type in 0..19 with N, CA and C is packed, every other residue is fixed environment and is copied bit for bit.
+ *   pos_out [B,N,15,3], mask_out [B,N,15]; packed [B,N]; rotamer [B,N] (-1: not packed); chi [B,N,4]; n_rotamers [B,N];
+ *   energy_self_best [B,N] (E_self of the start); energy_residue [B,N] (E_self + half the pair terms at the end);
+ *   energy_trace [B,sweeps+1] float64 ([0]: the start; sweeps not run repeat the last); sweeps_run [B]; changed [B,sweeps];
+ *   choice_trace [B,sweeps,N] optional: the rotamer taken at each visit (entries not visited are left as they are).
+ * work: pf_pack_work_bytes(B, N, max_rot) bytes, 16-byte aligned, no initialisation needed (-1: N > PF_PACK_MAX_N, max_rot outside
+ * 1 .. PF_PACK_MAX_ROT, a negative size, or more than INT_MAX bytes).  Three launches, no atomics, one writer per output, every sum in
+ * a fixed order, every decision an argmin under (value, index): bit-identical from run to run and independent of the rest of the
+ * batch; the host reads nothing back.  N > PF_PACK_MAX_N, max_rot > PF_PACK_MAX_ROT or B > 65535 -> PF_E_TOOLARGE. */
+#define PF_PACK_MAX_N 512
+#define PF_PACK_MAX_ROT 128
+#define PF_PACK_SLOTS 15
+#define PF_PACK_ROT_ATOMS 9
+typedef struct {
+    const float* pos;                                               /* [B,N,n_atoms,3] */
+    const unsigned char* atom_mask;                                 /* [B,N,n_atoms] */
+    const int64_t* aa;                                              /* [B,N] */
+    const int* residue_index;                                       /* [B,N] */
+    const unsigned char* movable;                                   /* [B,N] */
+    const float* radius;                                            /* [21,15] XS radii, 0: the type has no such atom */
+    const unsigned char* types;                                     /* [21,15] bit 0 hydrophobic, bit 1 donor, bit 2 acceptor */
+    const int* own_mask;                                            /* [21,15] bit b of (t, a): own-residue pair (a, b) is evaluated */
+    const float* tab_rot;                                           /* [21,8,9] the rigid groups' rotations */
+    const float* tab_trans;                                         /* [21,8,3] and translations */
+    const int* tab_group;                                           /* [21,14] rigid group of each slot */
+    const float* tab_pos;                                           /* [21,14,3] ideal position in its group's frame */
+    const unsigned char* tab_mask;                                  /* [22,15] the type's heavy atoms */
+    const float* rot_chi;                                           /* [21,max_rot,4] radians */
+    const int* rot_count;                                           /* [21] */
+    const float* rot_energy;                                        /* [21,max_rot] */
+    void* work;                                                     /* pf_pack_work_bytes(B, N, max_rot) bytes */
+    float* pos_out;                                                 /* [B,N,15,3] */
+    unsigned char* mask_out;                                        /* [B,N,15] */
+    unsigned char* packed;                                          /* [B,N] */
+    int* rotamer;                                                   /* [B,N] */
+    float* chi;                                                     /* [B,N,4] */
+    int* n_rotamers;                                                /* [B,N] */
+    float* energy_self_best;                                        /* [B,N] */
+    float* energy_residue;                                          /* [B,N] */
+    double* energy_trace;                                           /* [B,sweeps+1] */
+    int* sweeps_run;                                                /* [B] */
+    int* changed;                                                   /* [B,sweeps]; may be null when sweeps is 0 */
+    int* choice_trace;                                              /* [B,sweeps,N] optional */
+    int B, N, n_atoms, max_rot, sweeps, pro, cys;
+    float cutoff;                                                   /* > 0; 8.0 */
+    float w_gauss1, w_gauss2, w_repulsion, w_hydrophobic, w_hbond;  /* -0.0356, -0.00516, 0.840, -0.0351, -0.587 */
+} pf_pack_args;
+int pf_pack_sidechains_fwd(const pf_pack_args* a, pf_stream_t stream);
+int pf_pack_work_bytes(int B, int N, int max_rot);
+
 /* ---- empirical interface energy (ABI 64, added entry point) -----------------------------------------------------------------------
  * pf_interface_energy_fwd: the functional form of AutoDock Vina's scoring function (Trott & Olson, J. Comput. Chem. 2010) over the
  * heavy atoms of a batch of structures, between atoms of residues whose group bytes differ; the conventions are listed in

@@ -1163,3 +1163,196 @@ def relax(pos, atom_mask, aa, residue_index, movable, steps=200, **params):
     out["rmsd"] = torch.sqrt(sq.sum((1, 2)) / cnt.clamp(min=1.0))
     out["pos"] = new
     return out
+
+
+# Rotamer side-chain packing (conventions: csrc/packing.hip).  It is NOT SCWRL4 and NOT Rosetta's packer: there is no Dunbrack library
+# in this tree, the default rotamers are a staggered grid and the energy is this package's own Vina-form pair energy (`interface_energy`'s
+# pair function); it stands where the reference's evaluation packs a backbone-only sample with SCWRL4 (eval/run_scwrl4.py) in role only,
+# not in values.
+PACK_MAX_N = 512            # PF_PACK_MAX_N
+PACK_MAX_ROT = 128          # PF_PACK_MAX_ROT
+PACK_SLOTS = 15             # PF_PACK_SLOTS
+PACK_ROT_ATOMS = 9          # PF_PACK_ROT_ATOMS: slots 5..13
+# Stated from chemistry: the chi about a bond that ends on a planar (sp2) group; every other chi is about a bond between two
+# tetrahedral atoms.  Proline's ring has two puckers.
+PLANAR_CHI = {"ASN": 2, "ASP": 2, "GLN": 3, "GLU": 3, "HIS": 2, "PHE": 2, "TYR": 2, "TRP": 2}
+STAGGERED_DEG = (60.0, 180.0, 300.0)
+PRO_ROTAMERS_DEG = ((30.0, -35.0), (-30.0, 35.0))
+
+
+def rotamer_table(step_deg=30):
+    """-> (chi [21,R,4] float32 radians, count [21] int32, energy [21,R] float32 zeros), CPU tensors: the default rotamers of
+    `pack_sidechains`, a staggered grid and not a rotamer library.  Per residue type the product over its chi angles, chi1 slowest, each
+    ascending: a chi about a bond between two tetrahedral atoms takes 60, 180, 300 degrees; the terminal planar chi (PLANAR_CHI) takes
+    a step_deg grid over [0, 360), or [0, 180) where PI_PERIODIC_CHI says it is pi-periodic; PRO has the two rows PRO_ROTAMERS_DEG; ALA,
+    GLY and row 20 have one empty rotamer.  R is the largest count (108 at 30 degrees, GLN); rows beyond a type's count are zero."""
+    import itertools
+
+    from .preprocess import _tables
+    try:
+        step = float(step_deg)
+    except (TypeError, ValueError):
+        step = float("nan")
+    if not (math.isfinite(step) and 0.0 < step <= 180.0):
+        raise ValueError(f"step_deg must be a number in (0, 180], got {step_deg!r}")
+    index = _tables()["res_index"]
+    n_chi = (chi_atom_table()[:, :, 0] >= 0).sum(1)
+    rows = [[()] for _ in range(21)]
+    for name, t in index.items():
+        if t >= 20 or int(n_chi[t]) == 0:
+            continue
+        if name == "PRO":
+            rows[t] = [tuple(r) for r in PRO_ROTAMERS_DEG]
+            continue
+        axes = []
+        for k in range(1, int(n_chi[t]) + 1):
+            if PLANAR_CHI.get(name) == k:
+                period = 180.0 if PI_PERIODIC_CHI.get(name) == k else 360.0
+                grid, v = [], 0.0
+                while v < period - 1e-9:
+                    grid.append(v)
+                    v += step
+                axes.append(tuple(grid))
+            else:
+                axes.append(STAGGERED_DEG)
+        rows[t] = list(itertools.product(*axes))
+    count = torch.tensor([len(r) for r in rows], dtype=torch.int32)
+    R = int(count.max())
+    if R > PACK_MAX_ROT:
+        raise ValueError(f"step_deg = {step_deg!r} gives {R} rotamers for one residue type; at most {PACK_MAX_ROT}")
+    chi = torch.zeros(21, R, 4, dtype=torch.float64)
+    for t, rs in enumerate(rows):
+        for r, row in enumerate(rs):
+            for k, v in enumerate(row):
+                chi[t, r, k] = math.radians(v)
+    return chi.to(torch.float32), count, torch.zeros(21, R, dtype=torch.float32)
+
+
+def _rigid_group_table():
+    """-> [21,15] int64: atom14_group of data/rigid_groups.npz, slot 14 (OXT) with O"""
+    import os
+
+    import numpy as np
+
+    from .preprocess import _HERE
+    group = torch.from_numpy(np.load(os.path.join(_HERE, "data", "rigid_groups.npz"))["atom14_group"][:21]).to(torch.int64)
+    return torch.cat([group, group[:, 3:4]], 1)
+
+
+def packing_pair_table():
+    """-> [21,15,15] bool CPU tensor: entry (t, a, b) -- `pack_sidechains` evaluates the pair of slots a and b inside one residue of type
+    t: a is a rotamer atom (slots 5..13 in a chi1..chi4 rigid group), b is more than three bonds away from it in `bond_table`, and b is
+    N, CA, C, O, CB or OXT, or a rotamer atom of a smaller slot (each pair once).  Existing slots only; row 20 is empty."""
+    from .preprocess import _tables
+    names = _tables()["atom_names"]
+    bonds = bond_table().to(torch.int32)
+    eye = torch.eye(PACK_SLOTS, dtype=torch.int32)
+    step = ((bonds + eye) > 0).to(torch.int32)
+    within3 = (step @ step @ step) > 0
+    has = torch.tensor([[bool(names[t][s]) for s in range(PACK_SLOTS)] for t in range(20)] + [[False] * PACK_SLOTS])
+    rot = torch.zeros(21, PACK_SLOTS, dtype=torch.bool)
+    rot[:, 5:14] = (_rigid_group_table()[:, 5:14] >= 4) & has[:, 5:14]
+    a = torch.arange(PACK_SLOTS)
+    fixed = (a < 5) | (a == 14)
+    partner = fixed[None, None, :] | (rot[:, None, :] & (a[None, :] < a[:, None])[None])
+    return rot[:, :, None] & has[:, None, :] & ~within3 & partner
+
+
+def _pack_own_mask_table():
+    """-> [21,15] int32: bit b of (t, a) = packing_pair_table()[t, a, b], the form the kernel reads"""
+    bits = (1 << torch.arange(PACK_SLOTS, dtype=torch.int64))
+    return (packing_pair_table().to(torch.int64) * bits).sum(-1).to(torch.int32)
+
+
+def _check_rotamers(rotamers):
+    """-> (chi [21,R,4] float32, count [21] int32, energy [21,R] float32) CPU tensors, checked (ValueError)"""
+    try:
+        chi, count, energy = (torch.as_tensor(v).detach().cpu() for v in rotamers)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError("rotamers must be (chi [21,R,4], count [21], energy [21,R])") from None
+    R = chi.shape[1] if chi.dim() == 3 else -1
+    if chi.dim() != 3 or chi.shape[0] != 21 or chi.shape[2] != 4 or tuple(count.shape) != (21,) or tuple(energy.shape) != (21, R):
+        raise ValueError(f"rotamers must be (chi [21,R,4], count [21], energy [21,R]), got {tuple(chi.shape)}, {tuple(count.shape)}, "
+                         f"{tuple(energy.shape)}")
+    if R < 1 or R > PACK_MAX_ROT:
+        raise ValueError(f"a rotamer table holds 1 .. {PACK_MAX_ROT} rotamers per residue type, got R = {R}")
+    count = count.to(torch.int64)
+    if bool((count < 1).any()) or bool((count > R).any()):
+        raise ValueError(f"rotamer counts must be in 1 .. R = {R} (count <= {PACK_MAX_ROT}), got {count.tolist()}")
+    chi, energy = chi.to(torch.float32), energy.to(torch.float32)
+    if not bool(torch.isfinite(chi).all()) or not bool(torch.isfinite(energy).all()):
+        raise ValueError("rotamer chi and energy must be finite")
+    return chi.contiguous(), count.to(torch.int32).contiguous(), energy.contiguous()
+
+
+def _cysteine():
+    from .preprocess import residue_type
+    return residue_type("CYS")
+
+
+def pack_sidechains(pos, atom_mask, aa, residue_index, movable, rotamers=None, sweeps=8, cutoff=8.0, weights=VINA_WEIGHTS, trace=False):
+    """pf_pack_sidechains_fwd: rotamer side-chain packing of the movable residues on the device (conventions: csrc/packing.hip).  Every
+    rotamer of a discrete table is built on the residue's own backbone (the frame of N, CA, C and the ideal rigid groups of
+    `full_atom`; chi1 counts from the real N, so `torsion_angles` of the output gives `chi` back), scored with the pair function of `interface_energy` against the fixed environment, its own residue and the other
+    packed residues, and one rotamer per residue is chosen by iterated conditional modes.  It is NOT SCWRL4 and NOT Rosetta's packer:
+    no Dunbrack library (the default `rotamer_table` is a staggered grid), no hydrogens, no fitted parameter, a deterministic local
+    search and not the global minimum; it stands for them in role only.
+
+    Arguments as `relax`: pos [B,N,A,3], A >= 14; atom_mask [B,N,A]; aa [B,N]; residue_index [B,N]; movable [B,N]; N <= 512.  A
+    movable residue of a type in 0..19 whose N, CA and C are in atom_mask is packed; every other residue is fixed environment and
+    comes back bit for bit.  rotamers: (chi [21,R,4] radians, count [21], energy [21,R]) with R, count <= 128, e.g. a real library
+    with energy = -log p; None: `rotamer_table()`.  sweeps >= 0; cutoff and weights as `interface_energy`.
+    -> dict of device tensors: pos [B,N,15,3] float32 and atom_mask [B,N,15] bool (packed residues: N, CA, C, O and slot 14 as given,
+    CB rebuilt, slots 4..13 of the mask the type's); packed [B,N] bool; rotamer [B,N] int32 (-1 where not packed); chi [B,N,4] float32
+    (the chosen row); n_rotamers [B,N] int32; energy_self_best [B,N] float32 (the smallest E_self: the start); energy_residue [B,N]
+    float32 (E_self plus half of each of the residue's pair terms at the end); energy_trace [B,sweeps+1] float64 (the total after each
+    sweep, [0]: the start; sweeps not run repeat the last); sweeps_run [B] int32; changed [B,sweeps] int32 (rotamers changed in each
+    sweep); with trace=True also choice_trace [B,sweeps,N] int32 (the rotamer taken at each visit, -1 where none)."""
+    if movable is None or residue_index is None:
+        raise ValueError("pack_sidechains needs residue_index [B,N] and movable [B,N]")
+    if not isinstance(sweeps, int) or isinstance(sweeps, bool) or sweeps < 0:
+        raise ValueError(f"sweeps must be an integer >= 0, got {sweeps!r}")
+    cutoff, w = _positive("cutoff", cutoff), _weights(weights)
+    rot = None if rotamers is None else _check_rotamers(rotamers)
+    dev, (B, N, A), pos, atom_mask, (aa, residue_index, movable) = _structure(pos, atom_mask, (
+        ("aa", aa, torch.int64), ("residue_index", residue_index, torch.int32), ("movable", movable, torch.uint8)), max_n=PACK_MAX_N)
+    S = PACK_SLOTS
+    f32 = lambda *shape: torch.zeros(*shape, device=dev)  # noqa: E731
+    i32 = lambda *shape, fill=0: torch.full(shape, fill, dtype=torch.int32, device=dev)  # noqa: E731
+    out = {"pos": f32(B, N, S, 3), "atom_mask": torch.zeros(B, N, S, dtype=torch.uint8, device=dev),
+           "packed": torch.zeros(B, N, dtype=torch.uint8, device=dev), "rotamer": i32(B, N, fill=-1), "chi": f32(B, N, 4),
+           "n_rotamers": i32(B, N), "energy_self_best": f32(B, N), "energy_residue": f32(B, N),
+           "energy_trace": torch.zeros(B, sweeps + 1, dtype=torch.float64, device=dev), "sweeps_run": i32(B), "changed": i32(B, sweeps)}
+    if trace:
+        out["choice_trace"] = i32(B, sweeps, N, fill=-1)
+    if B and N:
+        from . import full_atom
+        if rot is None:
+            tabs = [_table("rotamer_" + k, dev, lambda k=k: dict(zip(("chi", "count", "energy"), rotamer_table()))[k])
+                    for k in ("chi", "count", "energy")]
+        else:
+            tabs = [t.to(dev) for t in rot]
+        R = tabs[0].shape[1]
+        rigid, frames = full_atom._tables(dev)
+        if frames != [3, 4, 5, 6, 7]:
+            raise _capi.PepflowHipError(f"rigid_groups.npz: the frames are {frames}, the packing kernel is written for [3, 4, 5, 6, 7]")
+        lib = _capi.load()
+        nbytes = lib.pf_pack_work_bytes(B, N, R)
+        if nbytes < 0:
+            raise ValueError(f"pack_sidechains: the workspace for B = {B}, N = {N}, {R} rotamers exceeds 2 GiB; pack the batch in parts")
+        a = _capi.PackArgs()
+        _bind_in(a, pos=pos, atom_mask=atom_mask, aa=aa, residue_index=residue_index, movable=movable)
+        a.radius = _table("xs_radius", dev, xs_radius_table).data_ptr()
+        a.types = _table("interface_types", dev, interface_type_table).data_ptr()
+        a.own_mask = _table("pack_own_mask", dev, _pack_own_mask_table).data_ptr()
+        a.tab_rot, a.tab_trans, a.tab_group, a.tab_pos, a.tab_mask = (rigid[k].data_ptr() for k in ("rot", "trans", "group", "pos", "mask"))
+        a.rot_chi, a.rot_count, a.rot_energy = (t.data_ptr() for t in tabs)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        a.work = work.data_ptr()
+        _bind_out(a, {("mask_out" if k == "atom_mask" else "pos_out" if k == "pos" else k): v for k, v in out.items()})
+        a.B, a.N, a.n_atoms, a.max_rot, a.sweeps, a.pro, a.cys = B, N, A, R, sweeps, _proline(), _cysteine()
+        a.cutoff = cutoff
+        a.w_gauss1, a.w_gauss2, a.w_repulsion, a.w_hydrophobic, a.w_hbond = w
+        _capi.check(lib.pf_pack_sidechains_fwd(C.byref(a), _capi.stream_ptr()), "pf_pack_sidechains_fwd")
+    _as_bool(out, "atom_mask", "packed")
+    return out

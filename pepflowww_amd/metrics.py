@@ -12,10 +12,12 @@ DockQ (`docking_quality`); an empirical peptide-receptor interface energy, the f
 written from the publication and not checked against that program (`binding_energy`); structural clusters of the samples of each
 complex, their representatives and the best-scored member of each (`cluster_samples`: gromos clustering after Daura et al. 1999, which
 follows the publication and is not checked against GROMACS, and single / complete / average linkage cut at a height, checked against
-scipy's fcluster(criterion="distance") as partitions only).
+scipy's fcluster(criterion="distance") as partitions only); rotamer side chains for a backbone-only sample, a staggered rotamer grid
+scored with the interface energy's pair function and chosen by iterated conditional modes, which is not SCWRL4 and not Rosetta's
+packer and takes their place in role only (`pack_samples`, and backbone="packed" in the structure metrics).
 
 Every per-residue, per-point and per-atom-pair operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd /
-pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_relax_fwd / pf_cluster_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
+pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_relax_fwd / pf_cluster_fwd / pf_pack_sidechains_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
@@ -57,14 +59,16 @@ def _group_sum(values, index, G, dtype=torch.float64):
 
 
 def _check_backbone(backbone):
-    if backbone not in ("full_atom", "frames"):
-        raise ValueError(f"backbone must be 'full_atom' or 'frames', got {backbone!r}")
+    if backbone not in ("full_atom", "frames", "packed"):
+        raise ValueError(f"backbone must be 'full_atom', 'frames' or 'packed', got {backbone!r}")
 
 
 def _complexes(final, batch, backbone="full_atom", index=False):
     """The two complexes the structure metrics compare.  The sample: generated residues rebuilt from the final state -- backbone
-    "full_atom": all heavy atoms (reconstruct_sample: rotmats, trans, angles, seqs), "frames": N, CA, C, O (reconstruct_sample_bb) --
-    with the context kept, types where(generate, seqs, seqs_1).  The native: pos_heavyatom / mask_heavyatom / seqs_1.
+    "full_atom": all heavy atoms (reconstruct_sample: rotmats, trans, angles, seqs), "frames": N, CA, C, O (reconstruct_sample_bb),
+    "packed": the "frames" complex with the generated residues' side chains placed by geometry.pack_sidechains with its defaults (a
+    staggered rotamer grid and the package's own pair energy; not SCWRL4, whose place it takes in role only) -- with the context
+    kept, types where(generate, seqs, seqs_1).  The native: pos_heavyatom / mask_heavyatom / seqs_1.
     `backbone` is checked before final / batch are touched.
     -> (device, res_mask, gen = generate_mask & res_mask, `residue_index` of the batch if `index` else None,
         (pos_s, mask_s, aa_s), (pos_n, mask_n, seqs_1))"""
@@ -80,8 +84,13 @@ def _complexes(final, batch, backbone="full_atom", index=False):
     else:
         pos_s, mask_s = full_atom.reconstruct_sample_bb(rotmats, trans, seqs, batch["chain_nb"].to(dev), batch["res_nb"].to(dev),
                                                         res_mask, gen, pos_n, mask_n)
-    idx = residue_index(batch["chain_nb"].to(dev), batch["res_nb"].to(dev), res_mask) if index else None
-    return dev, res_mask, gen, idx, (pos_s, mask_s, torch.where(gen, seqs, seqs_1)), (pos_n, mask_n, seqs_1)
+    packed = backbone == "packed"
+    idx = residue_index(batch["chain_nb"].to(dev), batch["res_nb"].to(dev), res_mask) if index or packed else None
+    aa_s = torch.where(gen, seqs, seqs_1)
+    if packed:
+        p = geometry.pack_sidechains(pos_s, mask_s & res_mask[:, :, None], aa_s, idx, gen)
+        pos_s, mask_s = p["pos"], torch.where(p["packed"][:, :, None], p["atom_mask"], mask_s)
+    return dev, res_mask, gen, idx if index else None, (pos_s, mask_s, aa_s), (pos_n, mask_n, seqs_1)
 
 
 def binding_site(ctx_pos, ctx_atom_mask, res_mask, gen_mask, pep_sample, pep_native, cutoff=BIND_CUTOFF, ca_atom=CA_ATOM):
@@ -257,7 +266,8 @@ def secondary_structure(final, batch, backbone="full_atom"):
     `evaluate_samples`; the peptide chain is generate_mask & res_mask.
 
     backbone: "full_atom" -- the sample's N, CA, C, O from full_atom_reconstruction(rotmats, trans, angles, seqs), as save_samples_sc
-    writes them; "frames" -- from reconstruct_backbone(rotmats, trans, seqs, chain_nb, res_nb, res_mask), as save_samples_bb does.
+    writes them; "frames" -- from reconstruct_backbone(rotmats, trans, seqs, chain_nb, res_nb, res_mask), as save_samples_bb does;
+    "packed" -- the same backbone as "frames" (packing places side chains and leaves N, CA, C, O where they are).
     Prolines come from seqs for the sample and from seqs_1 for the native, whose backbone is pos_heavyatom[..., :4, :]; a native
     residue missing one of those four atoms in mask_heavyatom counts as masked (and never agrees).
 
@@ -591,4 +601,52 @@ def relax_samples(final, batch, backbone="full_atom", steps=200, **params):
         t = e["terms"]
         out["energy" + etag] = e["energy"]
         out["clashing" + etag] = w[2] * t[:, 2] > (w[0] * t[:, 0] + w[1] * t[:, 1]).abs()
+    return out
+
+
+def pack_samples(final, batch, backbone="frames", **kw):
+    """Rotamer side-chain packing of each sample's generated residues against the fixed receptor on the device (geometry.
+    pack_sidechains: a staggered rotamer grid unless `rotamers` is given, the pair function of geometry.interface_energy, iterated
+    conditional modes; NOT SCWRL4 and NOT Rosetta's packer, whose place before the energies (eval/run_scwrl4.py) it takes in role
+    only), with the clash counts and the interface energy before and after and the packing table against the native.  final / batch
+    and the sample's complex are those of `binding_energy` with backbone "frames" (the default: a backbone-only run) or "full_atom"
+    (the model's own side chains are replaced); movable = generate_mask & res_mask, the index comes from `residue_index`, the types
+    are where(generate, seqs, seqs_1); kw (rotamers, sweeps, cutoff, weights) goes to geometry.pack_sidechains.
+
+    -> dict of device tensors: pos_heavyatom [B,L,15,3] float32 (the receptor's atoms bit-identical to the rebuilt complex),
+    mask_heavyatom [B,L,15] bool, chi [B,L,4] float32 (radians, the chosen rotamer's), rotamer [B,L] int32 (-1 where not packed),
+    energy_trace [B,sweeps+1] float64, sweeps_run [B]; clash_atoms_before, clash_atoms_after, clash_atoms_cross_before,
+    clash_atoms_cross_after [B] int64 (the generated residues' atoms that geometry.structural_violations flags, against any other
+    residue and against the receptor) and energy_before, energy_after [B] float64 (geometry.interface_energy between peptide and
+    receptor), on the complex as given and as packed; chi_mae, chi_correct [B,4] and residue_correct [B] of the packed complex
+    against the native (geometry.sidechain_compare, as `sidechain_packing` reports them: degrees, NaN where nothing is compared) --
+    the packing baseline to put next to the model's own angles."""
+    if backbone not in ("full_atom", "frames"):
+        raise ValueError(f"backbone must be 'full_atom' or 'frames', got {backbone!r}")
+    if "trace" in kw:
+        raise ValueError("pack_samples does not return the choice trace; call geometry.pack_sidechains for it")
+    sweeps = kw.get("sweeps", 8)
+    if not isinstance(sweeps, int) or isinstance(sweeps, bool) or sweeps < 0:      # checked before final / batch are touched
+        raise ValueError(f"sweeps must be an integer >= 0, got {sweeps!r}")
+    dev, res_mask, gen, index, (pos, mask, aa), (pos_n, mask_n, aa_n) = _complexes(final, batch, backbone, index=True)
+    mask = mask & res_mask[:, :, None]
+    r = geometry.pack_sidechains(pos, mask, aa, index, gen, **kw)
+    new_mask = torch.where(r["packed"][:, :, None], r["atom_mask"], mask)
+    out = {"pos_heavyatom": r["pos"], "mask_heavyatom": new_mask, "chi": r["chi"], "rotamer": r["rotamer"],
+           "energy_trace": r["energy_trace"], "sweeps_run": r["sweeps_run"]}
+    for tag, p, m in (("_before", pos, mask), ("_after", r["pos"], new_mask)):
+        v = geometry.structural_violations(p, m, aa, index, query=gen, group=gen)
+        out["clash_atoms" + tag] = (v["clash_atom"] & gen[:, :, None]).sum((1, 2))
+        out["clash_atoms_cross" + tag] = (v["clash_atom_cross"] & gen[:, :, None]).sum((1, 2))
+        out["energy" + tag] = geometry.interface_energy(p, m, aa, gen)["energy"]
+    sides = []
+    for p, m, t in ((r["pos"], new_mask, aa), (pos_n, mask_n, aa_n)):
+        ang = geometry.torsion_angles(p, m & res_mask[:, :, None], t, index)
+        sides.append(dict(pos=p, atom_mask=m & gen[:, :, None], aa=t, angles=ang["angles"], defined=ang["defined"] & gen[:, :, None]))
+    ids = torch.arange(gen.shape[0], dtype=torch.int32, device=dev)
+    c = geometry.sidechain_compare(sides[0], sides[1], torch.stack([ids, ids], 1))
+    deg, cnt = 180.0 / math.pi, c["err_count"].double()
+    out["chi_mae"] = (c["err_sum"] * deg / cnt)[:, 4:]
+    out["chi_correct"] = (c["within"].double() / cnt)[:, 4:]
+    out["residue_correct"] = c["res_correct"].double() / c["res_with_chi"].double()
     return out
