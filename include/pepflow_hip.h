@@ -753,6 +753,59 @@ int pf_ipa_bwd_pairs(const pf_ipa_bwd_args* a, pf_stream_t stream);
 int pf_ipa_bwd_points(const pf_ipa_bwd_args* a, pf_stream_t stream);
 int pf_ipa_headw_bwd(const float* g_gamma, const float* head_w, float* g_head_w, pf_stream_t stream);
 
+/* ---- optimizer step on the device (csrc/optimizer.hip): the block that follows loss.backward() in train.py:135-146 and
+ * train_ddp.py:144-155 -- NaN gradient entries count as 0, clip_grad_norm_(max_norm), torch.optim.Adam / AdamW -- over ALL parameter
+ * tensors in one call (three launches), with no host read.  Additive to ABI 65.
+ *   tables     Everything that describes a step lives in DEVICE memory; only pointers and counts are passed by value, so a captured
+ *              launch stays valid when lr (or anything else in a table) changes.
+ *                tensors [n_tensors]   pf_optim_tensor: the addresses of the parameter and of its gradient, the offsets (in floats) of
+ *                                      its exp_avg / exp_avg_sq into the two flat state buffers, numel, the row of its group, active.
+ *                                      A tensor with active == 0 (its gradient is None in this call) is left untouched, counter included.
+ *                hyper [(1 + n_groups) * 8]  float64 rows: row 0 = {max_norm, 0...} (max_norm <= 0 or NaN: no clipping), row 1 + g =
+ *                                      {lr, beta1, beta2, eps, weight_decay, decoupled (0 = Adam, L2; else AdamW), 0, 0} of group g.
+ *                chunks [n_chunks, 2]  (tensor, first element): a chunk is PF_OPTIM_CHUNK consecutive elements of ONE tensor (fewer at
+ *                                      its end), first element a multiple of PF_OPTIM_CHUNK; one workgroup handles one chunk.  Every
+ *                                      element of every tensor belongs to exactly one chunk.  Entries out of range are ignored.
+ *                steps [n_tensors]     int32 step counters, one per tensor as torch keeps them per parameter.
+ *   phase 1    per chunk: sum of g^2 over its slice accumulated in float64, NaN entries counted as 0; the NaN count; whether +-inf
+ *              was seen.  One partial per chunk into `work`, no atomics.
+ *   reduction  one workgroup adds the partials in a fixed order: total_norm = sqrt(sum), coef = min(1, max_norm / (total_norm + 1e-6))
+ *              (clip_grad_norm_'s formula, in float64), and advances steps[] of every active tensor by one (one thread per tensor).
+ *   phase 2    per element, g = coef * (isnan(g) ? 0 : g), t = the advanced counter, bc1 = 1 - beta1^t, bc2 = 1 - beta2^t in float64:
+ *                Adam:  g += wd p            AdamW:  p *= 1 - lr wd
+ *                m = beta1 m + (1 - beta1) g;   v = beta2 v + (1 - beta2) g^2;   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ *              with float64 scalars; the moments and the final subtraction are formed in float64 and every stored value is rounded
+ *              once; the quotient m / (sqrt(v) / sqrt(bc2) + eps) is formed in fp32 from the rounded moments.
+ *   inf guard  if any active gradient holds +-inf the whole update is skipped: parameters, both moments and every counter keep their
+ *              bits, result.skipped goes up by one and grad_norm reads +inf.  (torch would turn the inf entries into NaN parameters.)
+ *   gradients  are read-only: NaNs are not written back, the clip is applied in registers.
+ *   result     {float grad_norm (what clip_grad_norm_ returns), int nan_count, int skipped (running total), int 0}.
+ *   alignment  a tensor whose parameter, gradient and both state slices are 16-byte aligned moves in 16-byte accesses, any other
+ *              (4-byte aligned) tensor and every tail in 4-byte accesses; the element-to-thread map is the same in both, so the
+ *              results are not a function of the alignment.  numel need not be a multiple of 4.
+ *   determinism  every word has one writer and every sum one order: bit-identical from run to run; tensors are coupled only through
+ *              coef and the inf guard.
+ * work: pf_optim_work_bytes(n_chunks) bytes, 16-byte aligned (-1 for n_chunks < 1).  NULL tables, n_tensors / n_groups / n_chunks < 1:
+ * PF_E_BADARG. */
+#define PF_OPTIM_CHUNK 4096
+typedef struct {
+    float* param; const float* grad;
+    long long exp_avg_off, exp_avg_sq_off;
+    int numel, group, active, pad_;
+} pf_optim_tensor;
+typedef struct {
+    const pf_optim_tensor* tensors;
+    const double* hyper;
+    const int* chunks;
+    float* exp_avg; float* exp_avg_sq;
+    int* steps;
+    void* work;
+    int* result;
+    int n_tensors, n_groups, n_chunks;
+} pf_optim_args;
+int pf_optim_step(const pf_optim_args* a, pf_stream_t stream);
+int pf_optim_work_bytes(int n_chunks);
+
 /* ---- full-atom reconstruction of sampled residues: models_con/torsion.py:140-226 (+ get_heavyatom_mask 121-138 and
  * the context merge of sample.py:104-108).  Tables: the reference's idealised rigid groups (constants.py), 21 residue
  * types: tab_rot [21,8,9], tab_trans [21,8,3], tab_group [21,14] (int32), tab_pos [21,14,3], tab_mask [22,15] (uint8),

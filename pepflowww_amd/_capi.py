@@ -279,6 +279,11 @@ class EtBwdArgs(C.Structure):
                 ("g_h2", _fp), ("g_h1", _fp), ("g_x", _fp), ("npairs", C.c_longlong), ("m1", _fp), ("m2", _fp)]
 
 
+class OptimArgs(C.Structure):
+    _fields_ = [("tensors", _fp), ("hyper", _fp), ("chunks", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("steps", _fp), ("work", _fp),
+                ("result", _fp), ("n_tensors", _i), ("n_groups", _i), ("n_chunks", _i)]
+
+
 _SIGNATURES = {
     "pf_et_bwd_chain": ([C.POINTER(EtBwdArgs), _fp], _i),
     "pf_gemm_tn_cat": ([_fp, _i, _i, _fp, _fp, _fp, _i, _i, _fp, _i, _i, _fp, _i, _fp, C.c_longlong, _fp], _i),
@@ -339,6 +344,8 @@ _SIGNATURES = {
     "pf_ipa_bwd_softmax": ([C.POINTER(IpaBwdArgs), _fp], _i),
     "pf_ipa_bwd_points": ([C.POINTER(IpaBwdArgs), _fp], _i),
     "pf_ipa_headw_bwd": ([_fp, _fp, _fp, _fp], _i),
+    "pf_optim_step": ([C.POINTER(OptimArgs), _fp], _i),
+    "pf_optim_work_bytes": ([_i], _i),
     "pf_split_pack_f16_checked": ([_fp, _i, _i, _i, _i, _fp, _fp, _fp], _i),
     "pf_split_pack_f16_batch": ([_fp, _i, _i, _fp, _fp], _i),
     "pf_full_atom_fwd": ([C.POINTER(FullAtomArgs), _fp], _i),

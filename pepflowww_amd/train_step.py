@@ -102,14 +102,23 @@ class GraphedTrainStep:
         losses = step(batch, noise=None)                          # replay; model.parameters() have .grad set
         optimizer.step()
 
+    With optimizer=FusedAdam(...) (pepflowww_amd/optim.py) the NaN guard, the gradient clip and the Adam update are captured at the end
+    of the same graph, serially behind the backward: one replay is then a whole training iteration and nothing is left to call.
+    Data-parallel callers keep the optimizer OUT of the graph (no collective is captured): step(...); step.allreduce(); opt.step().
+
     Nothing of the capture depends on the contents of the first batch: masks, lengths and noise are read from the static buffers by
     every replay, so a later batch may be padded differently.  The two categorical draws of the step come from the device Philox
     stream (`seed`) unless the step was captured with given_draws=True: then every replay reads them from noise['expo'] [2,B,L,20]
     (parity tests replay the oracle's draws this way).  A replay whose noise does not match the captured form is refused.
     """
 
-    def __init__(self, model, batch, loss_weights, first_sample=0, generator=None, given_draws=False):
+    def __init__(self, model, batch, loss_weights, first_sample=0, generator=None, given_draws=False, optimizer=None):
         _capi.load()
+        if optimizer is not None:
+            from .optim import FusedAdam
+            if not isinstance(optimizer, FusedAdam):
+                raise TypeError("GraphedTrainStep(optimizer=...) captures a pepflowww_amd.optim.FusedAdam; any other optimizer steps outside the graph")
+        self.optimizer = optimizer
         for n, p in model.named_parameters():
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise ValueError(f"GraphedTrainStep reads parameters in place: {n} must be contiguous float32")
@@ -144,9 +153,18 @@ class GraphedTrainStep:
             self.losses = losses
             self.grads = {n: grads[n].reshape(sd[n].shape) for n in self.names if grads.get(n) is not None}
             del state
+            if optimizer is not None:                     # same stream, behind the backward: no new branch in the graph
+                optimizer.launch()
         self.n_launches = _capi.CALLS - calls0            # C-ABI calls of one captured step (a few of them launch two kernels)
         for n, p in model.named_parameters():
             p.grad = self.grads.get(n)
+        if optimizer is not None:
+            # the captured launches read their tables at REPLAY time: the static gradients' addresses are known only now
+            by_param = {id(p): self.grads.get(n) for n, p in model.named_parameters()}
+            self._opt_grads = [by_param.get(id(p)) for p in optimizer._params]
+            optimizer.sync_groups()
+            optimizer.sync_pointers(self._opt_grads)
+            self._opt_key = optimizer._table_key
         self.check_weight_range()
 
     def check_weight_range(self):
@@ -173,6 +191,11 @@ class GraphedTrainStep:
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,), generator=self.generator).item())
         self.seed.fill_(seed)
+        if self.optimizer is not None:                    # param_groups[i]['lr'] may have been written by a scheduler since the last replay
+            self.optimizer.sync_groups()
+            if self.optimizer._table_key is not self._opt_key:   # an eager optimizer.step() in between re-pointed the table: the
+                self.optimizer.sync_pointers(self._opt_grads)    # static gradients' addresses go back in (813 addresses: not per replay)
+                self._opt_key = self.optimizer._table_key
         self.graph.replay()
         # optimizer.zero_grad() defaults to set_to_none=True: re-bind the static gradient tensors after every replay so that
         # optimizer.step() / clip_grad_norm_ always see what the graph just wrote
