@@ -527,6 +527,34 @@ int pf_sampler_init(const pf_sampler_args* a, const float* rot0, const float* tr
 /* post-process the prediction (291-312), record it, then Euler step (316-343) unless last step;
  * increments *step */
 int pf_sampler_step(const pf_sampler_args* a, pf_stream_t stream);
+/* ---- conditioned sampling: partial start and per-residue constraints -----------------------
+ * The reference has NO such call (its sample(), flow_model.py:229-374, always starts from noise and applies its three switches to
+ * the whole peptide).  A partial start re-uses the interpolants of the TRAINING corruption (flow_model.py:125-158) to place the
+ * initial state between the drawn noise and a given state at time t0 = ts[0]: an off-label use of the trained flow.
+ * "Flag" below = the row's bit where res_flags is set, a->sample_* otherwise; it stands in exactly the expressions where
+ * pf_sampler_init / pf_sampler_step use a->sample_* (so a constant byte plane equals the scalar flags on every row).
+ * init, on a generated row whose flag is on, with partial:
+ *   trans_t = (1 - t0) * trans0 + t0 * start_trans          rot_t = geodesic(base = rot0, target = start_rot, t0)
+ *   ang_t = torus geodesic(ang0, start_ang, t0)              simplex_t = (1 - t0) * simplex0 + t0 * simplex_of(start_seq)
+ *   seq_t = draw 0 from simplex_t
+ *   (trans0 / simplex0, which the Euler steps subtract, stay the centred / scaled NOISE; no torsion mask at init, as in 262-267).
+ * aa_allowed: classes outside a row's set take no part in ANY categorical draw of that row (maximum, softmax sum, arg-max).
+ * cond == NULL, or partial = 0 with NULL planes: the bits of pf_sampler_init / pf_sampler_step. */
+typedef struct {
+    /* partial start: state interpolated between the drawn noise and this state at time ts[0] */
+    int partial;                   /* 0 = the state is the noise, as pf_sampler_init */
+    const float* start_rot;        /* [B*L,9]  read on generated rows only; required when partial */
+    const float* start_trans;      /* [B*L,3] */
+    const float* start_ang;        /* [B*L,5] */
+    const int64_t* start_seq;      /* [B*L]   */
+    /* per-residue constraints, each optional */
+    const uint8_t* res_flags;      /* [B*L] bit0 backbone, bit1 angles, bit2 sequence; NULL = a->sample_* on every row */
+    const uint32_t* aa_allowed;    /* [B*L] bit k: class k may be drawn on this row; NULL = all 20 */
+} pf_sampler_cond_args;
+int pf_sampler_init_cond(const pf_sampler_args* a, const pf_sampler_cond_args* c, const float* rot0, const float* trans0_raw,
+                         const float* ang0, const float* simplex0_raw, pf_stream_t stream);
+/* pf_sampler_step with the row's flags and allowed classes; ts may be any strictly increasing grid */
+int pf_sampler_step_cond(const pf_sampler_args* a, const pf_sampler_cond_args* c, pf_stream_t stream);
 
 /* stand-alone manifold steps (KAT surface): so3_utils.geodesic_t (500-520) and torus.tor_geodesic_t */
 int pf_so3_geodesic(const float* base, const float* target, const float* t, float* out, int n, pf_stream_t stream);

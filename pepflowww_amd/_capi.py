@@ -80,6 +80,11 @@ class SamplerArgs(C.Structure):
                 ("B", _i), ("L", _i), ("sample_bb", _i), ("sample_ang", _i), ("sample_seq", _i), ("seed_dev", _fp), ("sample_ids", _fp)]
 
 
+class SamplerCondArgs(C.Structure):
+    _fields_ = [("partial", _i), ("start_rot", _fp), ("start_trans", _fp), ("start_ang", _fp), ("start_seq", _fp),
+                ("res_flags", _fp), ("aa_allowed", _fp)]
+
+
 class TrainArgs(C.Structure):
     _fields_ = [("rot1", _fp), ("trans1", _fp), ("ang1", _fp), ("seq1", _fp), ("gen_mask", _fp), ("res_mask", _fp),
                 ("t_raw", _fp), ("rot0", _fp), ("trans0_raw", _fp), ("ang0", _fp), ("simplex0_raw", _fp),
@@ -311,6 +316,8 @@ _SIGNATURES = {
     "pf_edge_features_fwd": ([C.POINTER(EdgeFeatArgs), _fp], _i),
     "pf_sampler_init": ([C.POINTER(SamplerArgs), _fp, _fp, _fp, _fp, _fp], _i),
     "pf_sampler_step": ([C.POINTER(SamplerArgs), _fp], _i),
+    "pf_sampler_init_cond": ([C.POINTER(SamplerArgs), C.POINTER(SamplerCondArgs), _fp, _fp, _fp, _fp, _fp], _i),
+    "pf_sampler_step_cond": ([C.POINTER(SamplerArgs), C.POINTER(SamplerCondArgs), _fp], _i),
     "pf_train_corrupt_fwd": ([C.POINTER(TrainArgs), _fp], _i),
     "pf_train_losses_fwd": ([C.POINTER(TrainArgs), _fp], _i),
     "pf_train_losses_bwd": ([C.POINTER(TrainArgs), C.POINTER(TrainBwdArgs), _fp], _i),

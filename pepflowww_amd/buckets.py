@@ -109,6 +109,12 @@ def sub_noise(noise, idx, L0, Lk):
     return out
 
 
+def sub_cond(cond, idx, L0, Lk):
+    """The packed conditioning (sampler.make_cond) of the samples `idx`, residue axis cut / padded to Lk by inert rows, like the noise."""
+    from .sampler import fit_cond
+    return fit_cond(cond, L0, Lk, idx)
+
+
 _STREAMS = {}       # device index -> {n_buckets: [stream of bucket 0, ...]} chosen by BucketedSampler._choose_streams
 
 
@@ -127,9 +133,14 @@ class BucketedSampler:
         self._pad_rows = None
 
     # ---- set-up of one call ----------------------------------------------------------------------------------------------
-    def bind(self, batch, noise, L0, seed, first_sample, stamp=lambda name: None):
+    def bind(self, batch, noise, L0, seed, first_sample, stamp=lambda name: None, grid=None, cond=None):
         """batch / noise: the caller's ([B, L0, ...], not padded).  Builds (or fetches from the encoder's cache) one engine + sampler
-        per bucket, encodes each sub-batch into its engine's pair buffer and initialises the sampler states."""
+        per bucket, encodes each sub-batch into its engine's pair buffer and initialises the sampler states.  grid / cond: the call's
+        time grid (None: the reference's) and packed conditioning (sampler.make_cond), sliced and padded per bucket like the noise;
+        they stay in the samplers' own buffers, so the re-initialisation after the calibration probes is the conditioned one too."""
+        if grid is None:
+            from .sampler import make_grid
+            grid = make_grid(self.N)
         model, dev = self.model, batch["aa"].device
         self.samplers.clear()
         self.engines.clear()
@@ -148,11 +159,14 @@ class BucketedSampler:
             stamp("encode")
             eng.bind_context(node, edge, sb["res_mask"])
             stamp("bind")
-            smp = eng.sampler(self.N, self.flags)
+            smp = eng.sampler(self.N, self.flags, cond=cond is not None)
             smp.set_seed(seed, first_sample)
+            smp.set_grid(grid)
             ids = torch.as_tensor(idx, dtype=torch.int64) + int(first_sample)
             smp.set_sample_ids(ids)
             smp.set_context(R1, x1, ang1, seq1, sb["generate_mask"])
+            if cond is not None:
+                smp.set_cond(sub_cond(cond, idx, L0, Lk), (R1, x1, ang1, seq1))
             smp.init_state(nz)
             self._nz.append(nz)
             smp.L_out = Lk

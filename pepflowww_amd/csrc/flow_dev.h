@@ -121,14 +121,20 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
 
 // categorical draw = torch.multinomial(p + 1e-8, 1) = argmax((p + 1e-8) / E), E ~ Exp(1)
 // (layers.py:17-22).  logits -> softmax inside.  expo: 20 caller-supplied draws or NULL (Philox).
+// MASKED (the conditioned sampler, pf_sampler_*_cond): bit k of `allowed` says whether class k may be drawn.  A class outside the set
+// takes no part in the draw: not in the maximum, not in the softmax sum (it adds +0), not in the arg-max (its value is -1, every
+// allowed class's is > 0).  With all 20 bits set every operation and its order are those of the unmasked form: the same bits.
+constexpr uint32_t ALL_CLASSES = (1u << KCLS) - 1u;
+
+template <bool MASKED = false>
 __device__ __forceinline__ long long categorical_dev(const float* logit, const float* expo, uint64_t seed,
-                                                     long long gsample, int draw, int res) {
-    float mx = logit[0];
+                                                     long long gsample, int draw, int res, uint32_t allowed = ALL_CLASSES) {
+    float mx = (!MASKED || (allowed & 1u)) ? logit[0] : -INFINITY;
 #pragma unroll
-    for (int k = 1; k < KCLS; ++k) mx = fmaxf(mx, logit[k]);
+    for (int k = 1; k < KCLS; ++k) mx = (!MASKED || ((allowed >> k) & 1u)) ? fmaxf(mx, logit[k]) : mx;
     float e[KCLS], sum = 0.f;
 #pragma unroll
-    for (int k = 0; k < KCLS; ++k) { e[k] = expf(logit[k] - mx); sum += e[k]; }
+    for (int k = 0; k < KCLS; ++k) { e[k] = (!MASKED || ((allowed >> k) & 1u)) ? expf(logit[k] - mx) : 0.f; sum += e[k]; }
     float E[KCLS];
     if (expo) {
 #pragma unroll
@@ -143,10 +149,10 @@ __device__ __forceinline__ long long categorical_dev(const float* logit, const f
         }
     }
     int best = 0;
-    float bv = (e[0] / sum + 1e-8f) / E[0];
+    float bv = (!MASKED || (allowed & 1u)) ? (e[0] / sum + 1e-8f) / E[0] : -1.f;
 #pragma unroll
     for (int k = 1; k < KCLS; ++k) {
-        const float v = (e[k] / sum + 1e-8f) / E[k];
+        const float v = (!MASKED || ((allowed >> k) & 1u)) ? (e[k] / sum + 1e-8f) / E[k] : -1.f;
         if (v > bv) { bv = v; best = k; }
     }
     return best;
@@ -156,23 +162,32 @@ __device__ __forceinline__ long long categorical_dev(const float* logit, const f
 // the same logits): lane q < 5 evaluates classes 4q..4q+3 (one Philox block, four expf / logf each); the softmax sum and the
 // arg-max scan run lane after lane in ascending class order, so every rounding and every tie is resolved exactly as in the
 // serial form above -- the result is bit-identical, the long scalar chain (60 exp/log per draw) is ~4x shorter.
+// MASKED / allowed: as in categorical_dev (the mask is the row's, the same in all eight lanes); the lane-after-lane order is kept.
+template <bool MASKED = false>
 __device__ __forceinline__ long long categorical_oct(const float* logit, const float* expo, uint64_t seed, long long gsample,
-                                                     int draw, int res, int sub) {
-    float mx = logit[0];
+                                                     int draw, int res, int sub, uint32_t allowed = ALL_CLASSES) {
+    float mx = (!MASKED || (allowed & 1u)) ? logit[0] : -INFINITY;
 #pragma unroll
-    for (int k = 1; k < KCLS; ++k) mx = fmaxf(mx, logit[k]);
+    for (int k = 1; k < KCLS; ++k) mx = (!MASKED || ((allowed >> k) & 1u)) ? fmaxf(mx, logit[k]) : mx;
     const int q = sub < 5 ? sub : 4;                      // lanes 5..7 shadow lane 4 (their results are never taken)
     float lq[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {                         // logit[4q + k] without dynamic indexing of the register array
         float v = logit[k];
 #pragma unroll
-        for (int t = 1; t < 5; ++t) v = (q == t) ? logit[4 * t + k] : v;
+        for (int t = 1; t < 5; ++t) {
+            float x = logit[4 * t + k];
+            // (MASKED: the compiler otherwise turns this select of loads into ONE load from a selected address and keeps the 20 logits in
+            //  scratch memory for it -- 96 bytes per lane; the empty statement pins the value in a register, it emits no instruction)
+            if (MASKED) asm volatile("" : "+v"(x));
+            v = (q == t) ? x : v;
+        }
         lq[k] = v;
     }
+    const uint32_t aq = MASKED ? (allowed >> (4 * q)) & 15u : 15u;      // this lane's four classes
     float e[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) e[k] = expf(lq[k] - mx);
+    for (int k = 0; k < 4; ++k) e[k] = (!MASKED || ((aq >> k) & 1u)) ? expf(lq[k] - mx) : 0.f;
     // sum = (((0 + e0) + e1) + ...) + e19, lane after lane
     float run = 0.f;
 #pragma unroll
@@ -196,7 +211,7 @@ __device__ __forceinline__ long long categorical_oct(const float* logit, const f
     }
     float v[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = (e[k] / sum + 1e-8f) / E[k];
+    for (int k = 0; k < 4; ++k) v[k] = (!MASKED || ((aq >> k) & 1u)) ? (e[k] / sum + 1e-8f) / E[k] : -1.f;
     // arg-max scan in ascending class order with strict '>' (first maximum wins)
     float bv = 0.f;
     int best = 0;

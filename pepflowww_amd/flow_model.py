@@ -10,7 +10,7 @@ from torch import nn
 
 from . import _capi, featurize
 from .modules import EdgeEmbedder, GAEncoder, NodeEmbedder
-from .sampler import DeviceSampler, default_noise
+from .sampler import DeviceSampler, default_noise, fit_cond, make_cond
 from .train_forward import TrainForward, default_train_noise
 
 MAX_NUM_HEAVYATOMS = 15     # pepflow/modules/protein/constants.py:91
@@ -33,7 +33,8 @@ def _pad_axis1(v, n, value=0):
 
 def _pad_residues(batch, noise, L0, L):
     """Pad every per-residue tensor of the batch ([B, L0, ...]) and of the pre-drawn noise to L residues the way PaddingCollate
-    pads (zeros; aa -> 21; masks False).  Index plumbing only."""
+    pads (zeros; aa -> 21; masks False).  Index plumbing only.  (The packed conditioning of a conditioned call is padded beside it,
+    with inert rows: sampler.fit_cond.)"""
     out = {}
     for k, v in batch.items():
         if torch.is_tensor(v) and v.dim() >= 2 and v.shape[1] == L0:
@@ -157,8 +158,20 @@ class FlowModel(nn.Module):
 
     def _sample_impl(self, batch, num_steps=100, sample_bb=True, sample_ang=True, sample_seq=True, *,
                noise=None, seed=None, first_sample=0, use_graph=True, return_sampler=False, timings=None, pageable=False, check_range=True,
-               buckets="auto", gc_collect=True, calibrate=True, _gc_was_enabled=None):
+               buckets="auto", gc_collect=True, calibrate=True, t_start=None, ts=None, start=None, aa_allowed=None, _gc_was_enabled=None):
         """Reference signature + keyword-only extensions:
+        t_start      the time grid becomes linspace(t_start, 1, num_steps) instead of linspace(1e-2, 1, num_steps); 0 < t_start < 1;
+        ts           an explicit grid: num_steps strictly increasing values in (0, 1] (excludes t_start);
+        start        None: the initial state is pure noise, whatever the grid.  "native" (the batch's own peptide, i.e. the context
+                     encode() returns) or a dict with any of rotmats [B,L,3,3] / trans [B,L,3] / angles [B,L,5] / seqs [B,L] (the
+                     entries of a trajectory dict: start=traj[-1] works; a missing entry takes the native's value; CPU or device
+                     tensors): PARTIAL start -- the initial state of the generated residues is the training corruption's interpolant
+                     (flow_model.py:125-158) between the drawn noise and this state at the grid's first time.  Needs t_start or ts.
+                     The reference has no such call: an OFF-LABEL use of the trained flow (INTEGRATION.md);
+        sample_bb / sample_ang / sample_seq   each may be a bool [B, L] tensor instead of a bool: the switch per residue (scalars among
+                     them are broadcast);
+        aa_allowed   bool [20], [L, 20] or [B, L, 20]: the residue types that may be drawn (per residue); a residue that allows none
+                     raises ValueError;
         noise        dict(rot0, trans0, ang0, simplex0[, expo]) of pre-drawn noise (parity tests);
         seed         Philox seed for the in-kernel categorical draws (default: from torch's CPU generator); with noise=None an
                      explicit seed also keys the initial noise per GLOBAL sample index (distributed.seeded_noise);
@@ -198,6 +211,9 @@ class FlowModel(nn.Module):
         dev = batch["aa"].device
         B, L0 = batch["aa"].shape
         self.last_buckets = None                       # [(samples, padded length)] of the call when it was split by length
+        # the conditioning arguments, validated and packed on the host (sampler.make_cond): the grid of EVERY call, the three scalar
+        # switches, and `cond` = None for a call that uses none of the per-residue / partial-start arguments
+        grid, flags, cond = make_cond(B, L0, num_steps, sample_bb, sample_ang, sample_seq, t_start, ts, start, aa_allowed)
         if noise is None:
             if seed is None:
                 noise = default_noise(B, L0)          # torch's global CPU generator, like the reference (flow_model.py:252-277)
@@ -209,8 +225,9 @@ class FlowModel(nn.Module):
             edges = (_bk.FUSED_MAX_L,) if buckets == "auto" or buckets is True else tuple(buckets)
             plan = _bk.plan_length_buckets(_bk.sample_lengths(batch["res_mask"]), edges)
             if len(plan) > 1:
-                return self._sample_bucketed(plan, batch, num_steps, (sample_bb, sample_ang, sample_seq), noise, seed, first_sample,
-                                             use_graph, return_sampler, timings, pageable, check_range, stamp, gc_collect, calibrate, _gc_was_enabled)
+                return self._sample_bucketed(plan, batch, num_steps, flags, noise, seed, first_sample,
+                                             use_graph, return_sampler, timings, pageable, check_range, stamp, gc_collect, calibrate, _gc_was_enabled,
+                                             grid=grid, cond=cond)
         # Residue axis padded to a multiple of 16 internally (what PaddingCollate does to a shorter sample of a batch: pad values,
         # res_mask False -- padded residues are inert, tests/test_gpu_parity.py ragged cases): every kernel then runs its
         # full-tile path (16-row / 16-key tiles, float4 rows of the [B,8,L,L] buffers).  In-kernel random draws are keyed by
@@ -218,6 +235,7 @@ class FlowModel(nn.Module):
         L = (L0 + 15) // 16 * 16
         if L != L0:
             batch, noise = _pad_residues(batch, noise, L0, L)
+            cond = fit_cond(cond, L0, L)
         stamp("noise")
         # The engine (workspaces, launch plan), its sampler (trajectory buffers, captured graphs) and the packed weights are cached
         # (GAEncoder.engine / DenoiseEngine.sampler): a second call at a shape seen before only encodes, binds and replays.
@@ -229,9 +247,12 @@ class FlowModel(nn.Module):
         stamp("bind")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        smp = eng.sampler(num_steps, (sample_bb, sample_ang, sample_seq))
+        smp = eng.sampler(num_steps, flags, cond=cond is not None)
         smp.set_seed(seed, first_sample)
+        smp.set_grid(grid)
         smp.set_context(R1, x1, ang1, seq1, batch["generate_mask"])
+        if cond is not None:
+            smp.set_cond(cond, (R1, x1, ang1, seq1))
         smp.init_state(noise)
         stamp("setup")
         if use_graph and timings is not None and smp.needs_capture():
@@ -268,9 +289,9 @@ class FlowModel(nn.Module):
         return traj
 
     def _sample_bucketed(self, plan, batch, num_steps, flags, noise, seed, first_sample, use_graph, return_sampler, timings, pageable,
-                         check_range, stamp, gc_collect=True, calibrate=True, _gc_was_enabled=None):
+                         check_range, stamp, gc_collect=True, calibrate=True, _gc_was_enabled=None, grid=None, cond=None):
         """sample() of a ragged batch through its length buckets (pepflowww_amd/buckets.py): same inputs, noise, Philox streams and
-        output format as the unsplit path."""
+        output format as the unsplit path.  grid / cond: the call's time grid and packed conditioning (sampler.make_cond)."""
         from .buckets import BucketedSampler
         stamp("noise")
         B, L0 = batch["aa"].shape
@@ -279,7 +300,7 @@ class FlowModel(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         smp = BucketedSampler(self, plan, B, L, num_steps, flags)
         smp.calibrate = bool(calibrate)
-        smp.bind(batch, noise, L0, seed, first_sample, stamp)
+        smp.bind(batch, noise, L0, seed, first_sample, stamp, grid=grid, cond=cond)
         if use_graph and timings is not None and smp.needs_capture():
             smp.capture()
             stamp("capture")

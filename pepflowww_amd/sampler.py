@@ -43,11 +43,169 @@ def default_noise(B, L, generator=None):
             "simplex0": torch.randn(B, L, 20, generator=g)}
 
 
-class DeviceSampler:
-    """Owned by its engine (DenoiseEngine.sampler caches one per (num_steps, flags)): trajectory buffers and the captured graphs are
-    reused by the next sample() call; set_seed() / set_context() / init_state() are what a call changes."""
+# ---- conditioned sampling: host-side validation and packing (no GPU needed) ------------------------------------------------------
+# The reference's sample() (flow_model.py:229-374) has none of this: it starts from pure noise on linspace(1e-2, 1, num_steps), its three
+# switches cover the whole peptide, and any of the 20 residue types may be drawn.  A partial start places the initial state on the
+# training corruption's interpolants (flow_model.py:125-158) between the noise and a given state: an OFF-LABEL use of the trained flow.
+ALL_AA = (1 << 20) - 1                       # every class allowed (pf_sampler_cond_args.aa_allowed)
+FLAG_BB, FLAG_ANG, FLAG_SEQ = 1, 2, 4        # bits of pf_sampler_cond_args.res_flags
+_START_KEYS = {"rotmats": (3, 3), "trans": (3,), "angles": (5,), "seqs": ()}      # the entries of a trajectory dict a start may give
+COND_ROW_KEYS = ("res_flags", "aa_allowed") + tuple(_START_KEYS)                  # the per-residue tensors of a packed `cond`
+_COND_PAD = {"res_flags": 0, "aa_allowed": ALL_AA, "rotmats": 0, "trans": 0, "angles": 0, "seqs": 21}
 
-    def __init__(self, engine, num_steps, flags=(True, True, True), first_sample=0, seed=0):
+
+def make_grid(num_steps, t_start=None, ts=None):
+    """The time grid of a call as an fp32 CPU tensor [num_steps]: linspace(1e-2, 1, N) (flow_model.py:280), linspace(t_start, 1, N) for
+    0 < t_start < 1, or the caller's own strictly increasing `ts` in (0, 1].  ValueError otherwise."""
+    num_steps = int(num_steps)
+    if num_steps < 1:
+        raise ValueError(f"num_steps = {num_steps}: at least one step")
+    if ts is not None:
+        if t_start is not None:
+            raise ValueError("t_start and ts exclude each other: ts IS the grid")
+        g = torch.as_tensor(ts).detach().to("cpu", torch.float32)
+        if g.dim() != 1 or g.numel() != num_steps:
+            raise ValueError(f"ts: expected a 1-D grid of num_steps = {num_steps} values, got shape {tuple(g.shape)}")
+        if not (bool(g[0] > 0) and bool(g[-1] <= 1) and bool((g[1:] > g[:-1]).all())):
+            raise ValueError("ts: expected strictly increasing values in (0, 1]")
+        return g.clone().contiguous()
+    if t_start is None:
+        return torch.linspace(1e-2, 1.0, num_steps)
+    t = float(t_start)
+    if not 0.0 < t < 1.0:
+        raise ValueError(f"t_start = {t_start}: expected 0 < t_start < 1")
+    return torch.linspace(t, 1.0, num_steps)
+
+
+def pack_res_flags(sample_bb, sample_ang, sample_seq, B, L):
+    """-> (scalar flags, byte plane).  All three plain bools: (the bools, None).  Any bool [B, L] tensor among them: the scalars are
+    broadcast and the call runs on the uint8 [B, L] plane (bit 0 backbone, 1 angles, 2 sequence); the scalar flags are then unused
+    by the kernels and returned as all-True (one cached sampler serves every plane)."""
+    vals = (sample_bb, sample_ang, sample_seq)
+    if not any(torch.is_tensor(v) for v in vals):
+        return tuple(bool(v) for v in vals), None
+    plane = np.zeros((B, L), dtype=np.uint8)
+    for bit, (name, v) in enumerate(zip(("sample_bb", "sample_ang", "sample_seq"), vals)):
+        if torch.is_tensor(v):
+            if v.dtype != torch.bool or tuple(v.shape) != (B, L):
+                raise ValueError(f"{name}: expected a bool or a bool tensor [{B}, {L}], got {v.dtype} {tuple(v.shape)}")
+            m = v.detach().cpu().numpy()
+        else:
+            m = np.full((B, L), bool(v))
+        plane |= m.astype(np.uint8) << np.uint8(bit)
+    return (True, True, True), torch.from_numpy(plane)
+
+
+def pack_aa_allowed(aa_allowed, B, L):
+    """bool [20] / [L, 20] / [B, L, 20] -> int32 [B, L] with bit k = class k may be drawn; None -> None.  A row that allows no class
+    raises ValueError."""
+    if aa_allowed is None:
+        return None
+    m = torch.as_tensor(aa_allowed)
+    if m.dtype != torch.bool or m.dim() not in (1, 2, 3) or tuple(m.shape) != (B, L, 20)[3 - m.dim():]:
+        raise ValueError(f"aa_allowed: expected bool [20], [{L}, 20] or [{B}, {L}, 20], got {m.dtype} {tuple(m.shape)}")
+    a = np.broadcast_to(m.detach().cpu().numpy(), (B, L, 20))
+    bits = (a.astype(np.int64) << np.arange(20, dtype=np.int64)).sum(-1).astype(np.int32)
+    if (bits == 0).any():
+        b, l = np.argwhere(bits == 0)[0]
+        raise ValueError(f"aa_allowed: no class allowed at sample {b}, residue {l}")
+    return torch.from_numpy(np.ascontiguousarray(bits))
+
+
+def check_start(start, B, L):
+    """None -> None (pure noise); "native" -> {} (every entry from the batch's own peptide); a dict with any of rotmats [B,L,3,3],
+    trans [B,L,3], angles [B,L,5], seqs [B,L] (the entries of a trajectory dict; others are ignored, a missing one takes the
+    native's value) -> those entries as fp32 / int64 tensors on the device they came from.  seqs outside 0..21 raise (for a device
+    tensor that is one host read of its extremes)."""
+    if start is None:
+        return None
+    if isinstance(start, str):
+        if start != "native":
+            raise ValueError(f"start = {start!r}: expected None, 'native' or a dict")
+        return {}
+    if not isinstance(start, dict):
+        raise ValueError(f"start: expected None, 'native' or a dict, got {type(start).__name__}")
+    out = {}
+    for k, tail in _START_KEYS.items():
+        v = start.get(k)
+        if v is None:
+            continue
+        if not torch.is_tensor(v) or tuple(v.shape) != (B, L) + tail:
+            raise ValueError(f"start[{k!r}]: expected a tensor {(B, L) + tail}, got {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}")
+        if k == "seqs":
+            if v.dtype not in (torch.int64, torch.int32):
+                raise ValueError(f"start['seqs']: expected an integer tensor, got {v.dtype}")
+            # residue types 0..19; 20 (UNK) and 21 (PAD) as a batch's `aa` may hold them on context rows: like seq_to_simplex
+            # (flow_model.py:108-109) they give the simplex of no class.  Anything else is a mistake, not a residue type.
+            if v.numel() and not (0 <= int(v.min()) and int(v.max()) <= 21):
+                raise ValueError(f"start['seqs']: residue types must lie in 0..21, got {int(v.min())}..{int(v.max())}")
+            out[k] = v.detach().to(torch.int64)
+        else:
+            if not v.dtype.is_floating_point:
+                raise ValueError(f"start[{k!r}]: expected a floating-point tensor, got {v.dtype}")
+            out[k] = v.detach().to(torch.float32)
+    return out
+
+
+def make_cond(B, L, num_steps, sample_bb=True, sample_ang=True, sample_seq=True, t_start=None, ts=None, start=None, aa_allowed=None):
+    """Everything sample()'s conditioning arguments say, validated: (grid, scalar flags, cond).  cond is None for a call that uses none
+    of them beyond the grid, else a dict: "partial" (bool) and any of the per-residue tensors COND_ROW_KEYS at the caller's [B, L]."""
+    grid = make_grid(num_steps, t_start, ts)
+    flags, plane = pack_res_flags(sample_bb, sample_ang, sample_seq, B, L)
+    allowed = pack_aa_allowed(aa_allowed, B, L)
+    st = check_start(start, B, L)
+    if st is not None and t_start is None and ts is None:
+        raise ValueError("start needs a grid: pass t_start or ts (the state is placed at the grid's first time)")
+    if plane is None and allowed is None and st is None:
+        return grid, flags, None
+    cond = {"partial": st is not None}
+    if plane is not None:
+        cond["res_flags"] = plane
+    if allowed is not None:
+        cond["aa_allowed"] = allowed
+    cond.update(st or {})
+    return grid, flags, cond
+
+
+def fit_cond(cond, L0, Lk, idx=None):
+    """The packed conditioning of the samples `idx` (None: all) with the residue axis cut or padded from L0 to Lk by INERT rows: no
+    flag set, every class allowed, identity frame, zeros, residue type 21 (none of it is read: padded rows are not generated)."""
+    if cond is None:
+        return None
+    from .buckets import _fit, _rows
+    out = {"partial": cond["partial"]}
+    for k in COND_ROW_KEYS:
+        v = cond.get(k)
+        if v is None:
+            continue
+        w = _fit(v if idx is None else _rows(v, idx), L0, Lk, 1, _COND_PAD[k])
+        if k == "rotmats" and Lk > L0:
+            for d in range(3):
+                w[:, L0:, d, d] = 1
+        out[k] = w
+    return out
+
+
+def shard_cond_kwargs(kw, lo, hi, total):
+    """sample()'s conditioning keywords with every per-sample tensor ([total, ...]) cut to the shard [lo, hi)."""
+    out = dict(kw)
+    for k in ("sample_bb", "sample_ang", "sample_seq"):
+        if torch.is_tensor(out.get(k)) and out[k].dim() == 2 and out[k].shape[0] == total:
+            out[k] = out[k][lo:hi]
+    a = out.get("aa_allowed")
+    if a is not None and torch.as_tensor(a).dim() == 3 and torch.as_tensor(a).shape[0] == total:
+        out["aa_allowed"] = torch.as_tensor(a)[lo:hi]
+    if isinstance(out.get("start"), dict):
+        out["start"] = {k: (v[lo:hi] if k in _START_KEYS and torch.is_tensor(v) and v.dim() >= 2 and v.shape[0] == total else v)
+                        for k, v in out["start"].items()}
+    return out
+
+
+class DeviceSampler:
+    """Owned by its engine (DenoiseEngine.sampler caches one per (num_steps, flags, cond)): trajectory buffers and the captured graphs are
+    reused by the next sample() call; set_seed() / set_grid() / set_context() / set_cond() / init_state() are what a call changes."""
+
+    def __init__(self, engine, num_steps, flags=(True, True, True), first_sample=0, seed=0, cond=False):
         self.eng = engine
         self.lib = engine.lib
         self.N = num_steps
@@ -85,6 +243,14 @@ class DeviceSampler:
         self.sample_ids = e(B, dt=torch.int64)
         a.sample_ids = self.sample_ids.data_ptr()
         self.args = a
+        # conditioned calls (pf_sampler_*_cond): the constraint planes and the start state live in buffers THIS sampler owns, so the
+        # pointers a captured graph bakes in never move; a call only rewrites their contents (set_cond)
+        self.cond = bool(cond)
+        if self.cond:
+            self.res_flags, self.aa_allowed = e(rows, dt=torch.uint8), e(rows, dt=torch.int32)
+            self.start_rot, self.start_trans, self.start_ang = e(rows, 9), e(rows, 3), e(rows, 5)
+            self.start_seq = e(rows, dt=torch.int64)
+            self.cargs = _capi.SamplerCondArgs()
         self.graph = None
         self.graph_k = None
         self._graph_key = None
@@ -110,7 +276,37 @@ class DeviceSampler:
         """Everything a captured graph has baked in besides device pointers that never move: the plan (pointer of block 0's pair
         input), the projection's kernel choice (active_rows hint), key-end lists on / off, caller-supplied categorical noise."""
         eng = self.eng
-        return (eng.plan_version, eng.active_rows, eng.padded, self.args.expo)
+        key = (eng.plan_version, eng.active_rows, eng.padded, self.args.expo)
+        if self.cond:                                   # which constraint planes the step kernel was launched with (NULL or the buffer)
+            key += (self.cargs.res_flags, self.cargs.aa_allowed)
+        return key
+
+    def set_grid(self, grid):
+        """The call's time grid (fp32 CPU tensor [num_steps], sampler.make_grid) into the device buffer the kernels and the captured
+        graphs read.  EVERY call writes it: the sampler is cached, and a default call after a t_start call gets the default grid back."""
+        assert grid.shape == (self.N,) and grid.dtype == torch.float32, (grid.shape, grid.dtype)
+        self.ts.copy_(grid)
+
+    def set_cond(self, cond, native):
+        """The call's conditioning (sampler.make_cond, padded to the engine's length) into the owned buffers.  native = (R1, x1, ang1, seq1)
+        of encode(): the start state's default, entry by entry."""
+        assert self.cond, "a sampler built without cond=True has no constraint buffers"
+        rows, c = self.eng.rows, self.cargs
+        plane, allowed = cond.get("res_flags"), cond.get("aa_allowed")
+        if plane is not None:
+            self.res_flags.copy_(plane.reshape(rows))
+        if allowed is not None:
+            self.aa_allowed.copy_(allowed.reshape(rows))
+        c.res_flags = self.res_flags.data_ptr() if plane is not None else None
+        c.aa_allowed = self.aa_allowed.data_ptr() if allowed is not None else None
+        c.partial = int(bool(cond["partial"]))
+        if c.partial:
+            for buf, key, nat, w in ((self.start_rot, "rotmats", native[0], 9), (self.start_trans, "trans", native[1], 3),
+                                     (self.start_ang, "angles", native[2], 5), (self.start_seq, "seqs", native[3], 1)):
+                src = cond.get(key)
+                buf.copy_((nat if src is None else src).reshape(buf.shape))
+        c.start_rot, c.start_trans = self.start_rot.data_ptr(), self.start_trans.data_ptr()
+        c.start_ang, c.start_seq = self.start_ang.data_ptr(), self.start_seq.data_ptr()
 
     def set_context(self, R1, x1, ang1, seq1, gen_mask):
         rows = self.eng.rows
@@ -133,17 +329,26 @@ class DeviceSampler:
             self.args.expo = self.expo.data_ptr()
         else:
             self.expo, self.args.expo = None, None
-        rc = self.lib.pf_sampler_init(C.byref(self.args), rot0.data_ptr(), tr0.data_ptr(), ang0.data_ptr(),
-                                      sx0.data_ptr(), _capi.stream_ptr())
-        _capi.check(rc, "pf_sampler_init")
+        if self.cond:
+            rc = self.lib.pf_sampler_init_cond(C.byref(self.args), C.byref(self.cargs), rot0.data_ptr(), tr0.data_ptr(), ang0.data_ptr(),
+                                               sx0.data_ptr(), _capi.stream_ptr())
+            _capi.check(rc, "pf_sampler_init_cond")
+        else:
+            rc = self.lib.pf_sampler_init(C.byref(self.args), rot0.data_ptr(), tr0.data_ptr(), ang0.data_ptr(),
+                                          sx0.data_ptr(), _capi.stream_ptr())
+            _capi.check(rc, "pf_sampler_init")
         self._init_keep = (rot0, tr0, ang0, sx0)
         self._so = None                                # (a streamed trajectory copy belongs to ONE run from step 0; see run(stream_out=True))
         self._steps_done = 0
 
     def _one_step(self):
         self.eng.run(concurrent=self.CONCURRENT)
-        rc = self.lib.pf_sampler_step(C.byref(self.args), _capi.stream_ptr())
-        _capi.check(rc, "pf_sampler_step")
+        if self.cond:
+            rc = self.lib.pf_sampler_step_cond(C.byref(self.args), C.byref(self.cargs), _capi.stream_ptr())
+            _capi.check(rc, "pf_sampler_step_cond")
+        else:
+            rc = self.lib.pf_sampler_step(C.byref(self.args), _capi.stream_ptr())
+            _capi.check(rc, "pf_sampler_step")
 
     SKIP_CONTEXT_ROWS = True  # the last block's tail only produces the generated residues' predictions (set_context)
     CONCURRENT = False        # projection(b + 1) on a side stream beside EdgeTransition(b): measured slower (DenoiseEngine.run)
