@@ -556,6 +556,60 @@ int pf_sampler_init_cond(const pf_sampler_args* a, const pf_sampler_cond_args* c
 /* pf_sampler_step with the row's flags and allowed classes; ts may be any strictly increasing grid */
 int pf_sampler_step_cond(const pf_sampler_args* a, const pf_sampler_cond_args* c, pf_stream_t stream);
 
+/* ---- guided sampling: C-alpha potentials that steer the translation prediction (csrc/guidance.hip) ----------
+ * The reference has NO such call, and the trained flow has never seen a shifted prediction: an off-label use, like the partial start.
+ * The potentials play the role of RFdiffusion's guiding potentials; they are written here from the formulas below and are not checked
+ * against any other program.  Nothing was tuned on a trained checkpoint.
+ * One launch between the network and pf_sampler_step*: it writes a GUIDED copy of pred_trans, which the step kernel is then pointed at.
+ * Row classes of sample b (positions in Angstrom): movable M = gen_mask & res_mask & backbone flag (res_flags bit 0 when the plane is
+ * given, sample_bb otherwise), x = pred_trans there; every other row with res_mask has x = trans1; rows without res_mask take no part.
+ * P = gen_mask & res_mask (peptide), C = res_mask & ~gen_mask (context), H = hotspots & C.  With d_ij = |x_i - x_j|, terms in this order:
+ *   0 receptor_clash  w0 * sum_{i in P, j in C} max(0, r_receptor - d_ij)^2
+ *   1 self_clash      w1 * sum_{i < j in P, j - i >= min_sep} max(0, r_self - d_ij)^2
+ *   2 ca_bond         w2 * sum_{l, l+1 in P} max(0, |d - 3.8| - bond_tol)^2
+ *   3 hotspot         w3 * sum_{j in H} max(0, s_j - r_hotspot)^2,  s_j = -(1/beta) ln sum_{i in P} exp(-beta d_ij) (evaluated with the
+ *                     minimum subtracted; 0 when P is empty or beta <= 0)
+ *   4 restraint       sum_p w_p * [max(0, lo_p - d)^2 + max(0, d - hi_p)^2] over the sample's PF_GUIDE_MAX_PAIRS row pairs (either end
+ *                     peptide or context; w_p = 0 pads the list; a pair with an end outside res_mask takes no part)
+ * g_i = dE/dx_i on M, 0 elsewhere (a pair with d < 1e-6 gives its energy and no gradient).  t = ts[*step] (or t[b]),
+ * u = (t - t_on) / (1 - t_on), lambda = 0 for t < t_on, else scale * u^power (power 0, 1 or 2; power 0 = 1);
+ * shift_i = lambda g_i * min(1, max_shift / max(|lambda g_i|, 1e-12)); guided_trans_i = float(x_i - shift_i) on M, the bits of
+ * pred_trans on every other row -- and on a movable row whose shift is zero.
+ * Energies and gradients are accumulated in double, every sum in a fixed order, no atomics: two runs give the same bits.
+ * params (device float [PF_GUIDE_NPARAMS]): w0 w1 w2 w3 | r_receptor r_self min_sep bond_tol | r_hotspot beta scale t_on | power
+ * max_shift 0 0.  Everything the potentials depend on is read from device memory at run time: a captured graph serves later calls
+ * that rewrite the buffers' contents.
+ * Sampler mode (step != NULL): slot *step of energy [num_steps,B,5] and shift_max [num_steps,B] is written; *step >= num_steps returns
+ * without writing, as pf_sampler_step does.  Stand-alone mode (step == NULL): t [B], energy [B,5]; guided_trans, shift_max and grad
+ * (g, unscaled) are each optional.
+ * L > PF_GUIDE_MAX_L -> PF_E_TOOLARGE.  The restraint list lives in device memory, so it is the KERNEL that refuses an index outside
+ * [0, L): the pair takes no part and error[b] is set to -1 (the kernel never clears it). */
+#define PF_GUIDE_MAX_PAIRS 64
+#define PF_GUIDE_MAX_L 1024
+#define PF_GUIDE_NPARAMS 16
+#define PF_GUIDE_NTERMS 5
+typedef struct {
+    const float* pred_trans;       /* [B*L,3] the network's translation prediction */
+    const float* trans1;           /* [B*L,3] context translations */
+    const float* gen_mask;         /* [B*L] 1 = generated residue */
+    const float* res_mask;         /* [B*L] */
+    const uint8_t* res_flags;      /* optional [B*L]: bit 0 = backbone flag of the row (pf_sampler_cond_args.res_flags) */
+    const uint8_t* hotspots;       /* optional [B*L]: 1 = hot-spot residue (context rows only) */
+    const int* pair_idx;           /* optional [B,PF_GUIDE_MAX_PAIRS,2] residue indices of the restraints */
+    const float* pair_par;         /* [B,PF_GUIDE_MAX_PAIRS,3] lo, hi, weight; required with pair_idx */
+    const float* params;           /* [PF_GUIDE_NPARAMS] */
+    const float* ts;               /* sampler mode: time grid [num_steps] */
+    const int* step;               /* sampler mode: device step counter (pf_sampler_args.step); NULL = stand-alone */
+    const float* t;                /* stand-alone mode: [B] */
+    float* guided_trans;           /* [B*L,3] */
+    float* energy;                 /* [num_steps,B,5] / [B,5]: the terms of the UNGUIDED prediction */
+    float* shift_max;              /* [num_steps,B] / [B]: the largest |shift_i| of the sample */
+    float* grad;                   /* optional, stand-alone mode: [B*L,3] */
+    int* error;                    /* optional [B] */
+    int B, L, num_steps, sample_bb;
+} pf_guidance_args;
+int pf_guidance_fwd(const pf_guidance_args* a, pf_stream_t stream);
+
 /* stand-alone manifold steps (KAT surface): so3_utils.geodesic_t (500-520) and torus.tor_geodesic_t */
 int pf_so3_geodesic(const float* base, const float* target, const float* t, float* out, int n, pf_stream_t stream);
 int pf_so3_log(const float* rot, float* rotvec, int n, pf_stream_t stream);

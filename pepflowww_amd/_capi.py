@@ -16,6 +16,8 @@ ABI_VERSION = 65
 
 _fp = C.c_void_p
 _i = C.c_int
+# include/pepflow_hip.h, guided sampling
+GUIDE_MAX_PAIRS, GUIDE_MAX_L, GUIDE_NPARAMS, GUIDE_NTERMS = 64, 1024, 16, 5
 
 
 class LinearArgs(C.Structure):
@@ -83,6 +85,13 @@ class SamplerArgs(C.Structure):
 class SamplerCondArgs(C.Structure):
     _fields_ = [("partial", _i), ("start_rot", _fp), ("start_trans", _fp), ("start_ang", _fp), ("start_seq", _fp),
                 ("res_flags", _fp), ("aa_allowed", _fp)]
+
+
+class GuidanceArgs(C.Structure):
+    _fields_ = [("pred_trans", _fp), ("trans1", _fp), ("gen_mask", _fp), ("res_mask", _fp), ("res_flags", _fp), ("hotspots", _fp),
+                ("pair_idx", _fp), ("pair_par", _fp), ("params", _fp), ("ts", _fp), ("step", _fp), ("t", _fp),
+                ("guided_trans", _fp), ("energy", _fp), ("shift_max", _fp), ("grad", _fp), ("error", _fp),
+                ("B", _i), ("L", _i), ("num_steps", _i), ("sample_bb", _i)]
 
 
 class TrainArgs(C.Structure):
@@ -318,6 +327,7 @@ _SIGNATURES = {
     "pf_sampler_step": ([C.POINTER(SamplerArgs), _fp], _i),
     "pf_sampler_init_cond": ([C.POINTER(SamplerArgs), C.POINTER(SamplerCondArgs), _fp, _fp, _fp, _fp, _fp], _i),
     "pf_sampler_step_cond": ([C.POINTER(SamplerArgs), C.POINTER(SamplerCondArgs), _fp], _i),
+    "pf_guidance_fwd": ([C.POINTER(GuidanceArgs), _fp], _i),
     "pf_train_corrupt_fwd": ([C.POINTER(TrainArgs), _fp], _i),
     "pf_train_losses_fwd": ([C.POINTER(TrainArgs), _fp], _i),
     "pf_train_losses_bwd": ([C.POINTER(TrainArgs), C.POINTER(TrainBwdArgs), _fp], _i),

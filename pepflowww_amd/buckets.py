@@ -109,6 +109,13 @@ def sub_noise(noise, idx, L0, Lk):
     return out
 
 
+def sub_guide(guide, idx, L0, Lk):
+    """The packed guidance (sampler.make_guide) of the samples `idx`: their own restraint lists and hot spots, the plane cut / padded to
+    Lk; residue indices stay (padding is appended at the end)."""
+    from .sampler import fit_guide
+    return fit_guide(guide, L0, Lk, idx)
+
+
 def sub_cond(cond, idx, L0, Lk):
     """The packed conditioning (sampler.make_cond) of the samples `idx`, residue axis cut / padded to Lk by inert rows, like the noise."""
     from .sampler import fit_cond
@@ -133,11 +140,12 @@ class BucketedSampler:
         self._pad_rows = None
 
     # ---- set-up of one call ----------------------------------------------------------------------------------------------
-    def bind(self, batch, noise, L0, seed, first_sample, stamp=lambda name: None, grid=None, cond=None):
+    def bind(self, batch, noise, L0, seed, first_sample, stamp=lambda name: None, grid=None, cond=None, guide=None):
         """batch / noise: the caller's ([B, L0, ...], not padded).  Builds (or fetches from the encoder's cache) one engine + sampler
         per bucket, encodes each sub-batch into its engine's pair buffer and initialises the sampler states.  grid / cond: the call's
         time grid (None: the reference's) and packed conditioning (sampler.make_cond), sliced and padded per bucket like the noise;
-        they stay in the samplers' own buffers, so the re-initialisation after the calibration probes is the conditioned one too."""
+        they stay in the samplers' own buffers, so the re-initialisation after the calibration probes is the conditioned one too.
+        guide: the call's packed guidance (sampler.make_guide), sliced per bucket the same way."""
         if grid is None:
             from .sampler import make_grid
             grid = make_grid(self.N)
@@ -159,7 +167,7 @@ class BucketedSampler:
             stamp("encode")
             eng.bind_context(node, edge, sb["res_mask"])
             stamp("bind")
-            smp = eng.sampler(self.N, self.flags, cond=cond is not None)
+            smp = eng.sampler(self.N, self.flags, cond=cond is not None, guide=guide is not None)
             smp.set_seed(seed, first_sample)
             smp.set_grid(grid)
             ids = torch.as_tensor(idx, dtype=torch.int64) + int(first_sample)
@@ -167,6 +175,8 @@ class BucketedSampler:
             smp.set_context(R1, x1, ang1, seq1, sb["generate_mask"])
             if cond is not None:
                 smp.set_cond(sub_cond(cond, idx, L0, Lk), (R1, x1, ang1, seq1))
+            if guide is not None:
+                smp.set_guide(sub_guide(guide, idx, L0, Lk))
             smp.init_state(nz)
             self._nz.append(nz)
             smp.L_out = Lk
@@ -302,6 +312,15 @@ class BucketedSampler:
         self._nz = []                                                         # (the buckets' noise is not kept alive beyond the calibration)
         torch.cuda.synchronize()
         return by_role(*cache[ckey])
+
+    def guidance(self):
+        """The buckets' guidance records in the caller's sample order (DeviceSampler.guidance)."""
+        recs = [s.guidance() for s in self.samplers]
+        energy = torch.zeros(self.N, self.eng.B, recs[0]["energy"].shape[-1])
+        shift = torch.zeros(self.N, self.eng.B)
+        for rec, (idx, _) in zip(recs, self.plan):
+            energy[:, idx], shift[:, idx] = rec["energy"], rec["shift_max"]
+        return {"energy": energy, "shift_max": shift, "terms": recs[0]["terms"]}
 
     def operand_range(self):
         reps = [e.operand_range() for e in self.engines]

@@ -175,8 +175,10 @@ def sample_sharded(model, batch, num_steps=100, *, noise=None, seed=None, group=
     nz = shard_noise(noise, lo, hi) if noise is not None else seeded_noise(lo, hi, L, seed)
     sizes = [shard_bounds(total, world, r)[1] - shard_bounds(total, world, r)[0] for r in range(world)]
     if hi > lo:
-        from .sampler import shard_cond_kwargs
+        from .sampler import shard_cond_kwargs, shard_guide
         kw = shard_cond_kwargs(kw, lo, hi, total)      # per-sample conditioning (row flags, allowed classes, start state): this shard's rows
+        if kw.get("guide") is not None:
+            kw["guide"] = shard_guide(kw["guide"], lo, hi, total)      # ... and this shard's hot spots and restraint lists
         smp = model.sample(local, num_steps, noise=nz, seed=seed, first_sample=lo, return_sampler=True, **kw)
         packed = _final_state_of(smp)
     else:

@@ -10,7 +10,7 @@ from torch import nn
 
 from . import _capi, featurize
 from .modules import EdgeEmbedder, GAEncoder, NodeEmbedder
-from .sampler import DeviceSampler, default_noise, fit_cond, make_cond
+from .sampler import DeviceSampler, default_noise, fit_cond, fit_guide, make_cond, make_guide
 from .train_forward import TrainForward, default_train_noise
 
 MAX_NUM_HEAVYATOMS = 15     # pepflow/modules/protein/constants.py:91
@@ -158,7 +158,7 @@ class FlowModel(nn.Module):
 
     def _sample_impl(self, batch, num_steps=100, sample_bb=True, sample_ang=True, sample_seq=True, *,
                noise=None, seed=None, first_sample=0, use_graph=True, return_sampler=False, timings=None, pageable=False, check_range=True,
-               buckets="auto", gc_collect=True, calibrate=True, t_start=None, ts=None, start=None, aa_allowed=None, _gc_was_enabled=None):
+               buckets="auto", gc_collect=True, calibrate=True, t_start=None, ts=None, start=None, aa_allowed=None, guide=None, _gc_was_enabled=None):
         """Reference signature + keyword-only extensions:
         t_start      the time grid becomes linspace(t_start, 1, num_steps) instead of linspace(1e-2, 1, num_steps); 0 < t_start < 1;
         ts           an explicit grid: num_steps strictly increasing values in (0, 1] (excludes t_start);
@@ -172,6 +172,14 @@ class FlowModel(nn.Module):
                      them are broadcast);
         aa_allowed   bool [20], [L, 20] or [B, L, 20]: the residue types that may be drawn (per residue); a residue that allows none
                      raises ValueError;
+        guide        None, or a dict that switches GUIDED sampling on: C-alpha potentials evaluated on the device at every step shift
+                     the translation prediction the Euler step moves towards (csrc/guidance.hip; formulas: INTEGRATION.md).  Entries:
+                     weights (dict by term name or four numbers: receptor_clash, self_clash, ca_bond, hotspot; default 0 each),
+                     r_receptor=4.5, r_self=4.5, min_sep=3, bond_tol=0.1, r_hotspot=8.0, beta=1.0, hotspots (bool [L] or [B,L], context
+                     residues), restraints (one list for all samples, or one list per sample, of (i, j, lo, hi, weight); at most 64),
+                     scale=1.0, t_on=0.0, power=1 (0, 1 or 2), max_shift=2.0 (Angstrom per step).  Afterwards `model.last_guidance` =
+                     {"energy": [num_steps,B,5], "shift_max": [num_steps,B], "terms": names} (CPU tensors).  The reference has no
+                     such call: an OFF-LABEL use of the trained flow, and the defaults are starting values, not tuned ones;
         noise        dict(rot0, trans0, ang0, simplex0[, expo]) of pre-drawn noise (parity tests);
         seed         Philox seed for the in-kernel categorical draws (default: from torch's CPU generator); with noise=None an
                      explicit seed also keys the initial noise per GLOBAL sample index (distributed.seeded_noise);
@@ -214,6 +222,8 @@ class FlowModel(nn.Module):
         # the conditioning arguments, validated and packed on the host (sampler.make_cond): the grid of EVERY call, the three scalar
         # switches, and `cond` = None for a call that uses none of the per-residue / partial-start arguments
         grid, flags, cond = make_cond(B, L0, num_steps, sample_bb, sample_ang, sample_seq, t_start, ts, start, aa_allowed)
+        guide = make_guide(guide, B, L0, batch.get("generate_mask"), batch.get("res_mask"))
+        self.last_guidance = None                      # the per-step energies and largest shifts of a guided call
         if noise is None:
             if seed is None:
                 noise = default_noise(B, L0)          # torch's global CPU generator, like the reference (flow_model.py:252-277)
@@ -227,7 +237,7 @@ class FlowModel(nn.Module):
             if len(plan) > 1:
                 return self._sample_bucketed(plan, batch, num_steps, flags, noise, seed, first_sample,
                                              use_graph, return_sampler, timings, pageable, check_range, stamp, gc_collect, calibrate, _gc_was_enabled,
-                                             grid=grid, cond=cond)
+                                             grid=grid, cond=cond, guide=guide)
         # Residue axis padded to a multiple of 16 internally (what PaddingCollate does to a shorter sample of a batch: pad values,
         # res_mask False -- padded residues are inert, tests/test_gpu_parity.py ragged cases): every kernel then runs its
         # full-tile path (16-row / 16-key tiles, float4 rows of the [B,8,L,L] buffers).  In-kernel random draws are keyed by
@@ -236,6 +246,7 @@ class FlowModel(nn.Module):
         if L != L0:
             batch, noise = _pad_residues(batch, noise, L0, L)
             cond = fit_cond(cond, L0, L)
+            guide = fit_guide(guide, L0, L)
         stamp("noise")
         # The engine (workspaces, launch plan), its sampler (trajectory buffers, captured graphs) and the packed weights are cached
         # (GAEncoder.engine / DenoiseEngine.sampler): a second call at a shape seen before only encodes, binds and replays.
@@ -247,12 +258,14 @@ class FlowModel(nn.Module):
         stamp("bind")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        smp = eng.sampler(num_steps, flags, cond=cond is not None)
+        smp = eng.sampler(num_steps, flags, cond=cond is not None, guide=guide is not None)
         smp.set_seed(seed, first_sample)
         smp.set_grid(grid)
         smp.set_context(R1, x1, ang1, seq1, batch["generate_mask"])
         if cond is not None:
             smp.set_cond(cond, (R1, x1, ang1, seq1))
+        if guide is not None:
+            smp.set_guide(guide)
         smp.init_state(noise)
         stamp("setup")
         if use_graph and timings is not None and smp.needs_capture():
@@ -282,6 +295,8 @@ class FlowModel(nn.Module):
                               RuntimeWarning, stacklevel=2)
             stamp("range_check")
         smp.L_out = L0
+        if guide is not None:
+            self.last_guidance = smp.guidance()
         if return_sampler:
             return smp                                 # (owned by the engine: the next sample() call at this shape reuses it)
         traj = smp.trajectory(pageable=pageable)
@@ -289,9 +304,10 @@ class FlowModel(nn.Module):
         return traj
 
     def _sample_bucketed(self, plan, batch, num_steps, flags, noise, seed, first_sample, use_graph, return_sampler, timings, pageable,
-                         check_range, stamp, gc_collect=True, calibrate=True, _gc_was_enabled=None, grid=None, cond=None):
+                         check_range, stamp, gc_collect=True, calibrate=True, _gc_was_enabled=None, grid=None, cond=None, guide=None):
         """sample() of a ragged batch through its length buckets (pepflowww_amd/buckets.py): same inputs, noise, Philox streams and
-        output format as the unsplit path.  grid / cond: the call's time grid and packed conditioning (sampler.make_cond)."""
+        output format as the unsplit path.  grid / cond / guide: the call's time grid, packed conditioning (sampler.make_cond) and
+        packed guidance (sampler.make_guide)."""
         from .buckets import BucketedSampler
         stamp("noise")
         B, L0 = batch["aa"].shape
@@ -300,7 +316,7 @@ class FlowModel(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         smp = BucketedSampler(self, plan, B, L, num_steps, flags)
         smp.calibrate = bool(calibrate)
-        smp.bind(batch, noise, L0, seed, first_sample, stamp, grid=grid, cond=cond)
+        smp.bind(batch, noise, L0, seed, first_sample, stamp, grid=grid, cond=cond, guide=guide)
         if use_graph and timings is not None and smp.needs_capture():
             smp.capture()
             stamp("capture")
@@ -321,6 +337,8 @@ class FlowModel(nn.Module):
             stamp("range_check")
         smp.L_out = L0
         self.last_buckets = [(len(idx), Lk) for idx, Lk in plan]
+        if guide is not None:
+            self.last_guidance = smp.guidance()
         if return_sampler:
             return smp
         traj = smp.trajectory(pageable=pageable)

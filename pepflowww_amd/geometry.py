@@ -1356,3 +1356,64 @@ def pack_sidechains(pos, atom_mask, aa, residue_index, movable, rotamers=None, s
         _capi.check(lib.pf_pack_sidechains_fwd(C.byref(a), _capi.stream_ptr()), "pf_pack_sidechains_fwd")
     _as_bool(out, "atom_mask", "packed")
     return out
+
+
+# Guiding potentials of the sampler on their own (conventions and formulas: csrc/guidance.hip, include/pepflow_hip.h).  They stand
+# where RFdiffusion's guiding potentials stand, in role only: written from their formulas, checked against no other program.
+CA_POTENTIAL_MAX_L = _capi.GUIDE_MAX_L
+
+
+def ca_potential(x, peptide, movable, context, hotspots=None, restraints=None, t=1.0, **params):
+    """pf_guidance_fwd in its stand-alone mode: the five C-alpha potentials `FlowModel.sample(guide=...)` steers with, and their
+    gradient, evaluated once on given positions.
+
+    x [B,L,3] C-alpha positions in Angstrom (device tensor); peptide, movable, context: bool [B,L] -- the peptide rows, the ones among
+    them that may move (a subset of peptide) and the context rows (disjoint from peptide); rows in neither take no part.  hotspots:
+    bool [L] or [B,L], context rows; restraints: one list for all samples, or one list per sample, of (i, j, lo, hi, weight), at most
+    64.  t: the flow time the shift's schedule is evaluated at, a number or [B].  params: the entries of `sample()`'s guide dict
+    (sampler.GUIDE_DEFAULTS: weights, r_receptor, r_self, min_sep, bond_tol, r_hotspot, beta, scale, t_on, power, max_shift).
+    -> dict of device tensors: energy [B,5] (sampler.GUIDE_TERMS: receptor_clash, self_clash, ca_bond, hotspot, restraint), grad [B,L,3]
+    (dE/dx on movable rows, zero elsewhere), guided [B,L,3] (x - the clipped shift on movable rows, the bits of x elsewhere),
+    shift_max [B]."""
+    from . import sampler as S
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[-1] != 3:
+        raise ValueError(f"x must be a tensor [B,L,3], got {tuple(getattr(x, 'shape', ()))}")
+    B, L = x.shape[:2]
+    if L > CA_POTENTIAL_MAX_L:
+        raise ValueError(f"L = {L}: at most {CA_POTENTIAL_MAX_L} residues")
+    masks = {}
+    for name, m in (("peptide", peptide), ("movable", movable), ("context", context)):
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.bool or tuple(m.shape) != (B, L):
+            raise ValueError(f"{name} must be a bool tensor [{B},{L}], got {getattr(m, 'dtype', type(m).__name__)} {tuple(getattr(m, 'shape', ()))}")
+        masks[name] = m.detach().cpu()
+    if bool((masks["movable"] & ~masks["peptide"]).any()):
+        raise ValueError("movable must be a subset of peptide")
+    if bool((masks["context"] & masks["peptide"]).any()):
+        raise ValueError("context and peptide must be disjoint")
+    guide = S.make_guide({**params, "hotspots": hotspots, "restraints": restraints}, B, L, masks["peptide"], masks["peptide"] | masks["context"])
+    dev = x.device
+    x = _f32(x, dev)
+    tt = torch.as_tensor(t, dtype=torch.float32).reshape(-1)
+    if tt.numel() not in (1, B):
+        raise ValueError(f"t must be a number or [{B}] values, got {tt.numel()}")
+    tt = tt.expand(B).contiguous().to(dev)
+    f32 = lambda *shape: torch.empty(*shape, device=dev)  # noqa: E731
+    out = {"energy": f32(B, _capi.GUIDE_NTERMS), "grad": f32(B, L, 3), "guided": f32(B, L, 3), "shift_max": f32(B)}
+    if not (B and L):
+        for v in out.values():
+            v.zero_()
+        return out
+    gen, res = _f32(masks["peptide"], dev), _f32(masks["peptide"] | masks["context"], dev)
+    flags = _bytes(masks["movable"], dev)
+    keep = {k: (None if v is None else v.to(dev).contiguous()) for k, v in guide.items()}
+    err = torch.zeros(B, dtype=torch.int32, device=dev)
+    a = _capi.GuidanceArgs()
+    _bind_in(a, pred_trans=x, trans1=x, gen_mask=gen, res_mask=res, res_flags=flags, hotspots=keep["hotspots"],
+             pair_idx=keep["pair_idx"], pair_par=keep["pair_par"], params=keep["params"], t=tt)
+    a.guided_trans, a.energy, a.shift_max, a.grad, a.error = (out["guided"].data_ptr(), out["energy"].data_ptr(), out["shift_max"].data_ptr(),
+                                                            out["grad"].data_ptr(), err.data_ptr())
+    a.B, a.L, a.num_steps, a.sample_bb = B, L, 0, 1
+    _capi.check(_capi.load().pf_guidance_fwd(C.byref(a), _capi.stream_ptr()), "pf_guidance_fwd")
+    if bool((err != 0).any()):
+        raise _capi.PepflowHipError("pf_guidance_fwd refused a restraint index outside the sample")
+    return out

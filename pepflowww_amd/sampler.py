@@ -201,11 +201,153 @@ def shard_cond_kwargs(kw, lo, hi, total):
     return out
 
 
-class DeviceSampler:
-    """Owned by its engine (DenoiseEngine.sampler caches one per (num_steps, flags, cond)): trajectory buffers and the captured graphs are
-    reused by the next sample() call; set_seed() / set_grid() / set_context() / set_cond() / init_state() are what a call changes."""
+# ---- guided sampling: host-side validation and packing (no GPU needed) -----------------------------------------------------------
+# C-alpha potentials that shift the translation prediction of every step (csrc/guidance.hip; formulas: include/pepflow_hip.h and
+# INTEGRATION.md).  The reference has none of this: like the partial start an OFF-LABEL use of the trained flow.  The defaults are
+# starting values: nothing has been tuned on a trained checkpoint.
+GUIDE_TERMS = ("receptor_clash", "self_clash", "ca_bond", "hotspot", "restraint")
+GUIDE_DEFAULTS = {"weights": None, "r_receptor": 4.5, "r_self": 4.5, "min_sep": 3, "bond_tol": 0.1, "r_hotspot": 8.0, "beta": 1.0,
+                  "hotspots": None, "restraints": None, "scale": 1.0, "t_on": 0.0, "power": 1, "max_shift": 2.0}
+# slots of the device parameter vector (pf_guidance_args.params): the four weights first
+_GUIDE_SLOTS = ("r_receptor", "r_self", "min_sep", "bond_tol", "r_hotspot", "beta", "scale", "t_on", "power", "max_shift")
 
-    def __init__(self, engine, num_steps, flags=(True, True, True), first_sample=0, seed=0, cond=False):
+
+def _guide_weights(w):
+    """weights of terms 0-3: None, a dict by term name or a sequence of four -> four floats >= 0"""
+    if w is None:
+        return [0.0] * 4
+    if isinstance(w, dict):
+        for k in w:
+            if k not in GUIDE_TERMS[:4]:
+                raise ValueError(f"guide['weights']: unknown term {k!r}; the weighted terms are {GUIDE_TERMS[:4]} (a restraint carries its own weight)")
+        w = [w.get(k, 0.0) for k in GUIDE_TERMS[:4]]
+    w = [float(v) for v in w]
+    if len(w) != 4:
+        raise ValueError(f"guide['weights']: expected the weights of {GUIDE_TERMS[:4]}, got {len(w)} values")
+    for k, v in zip(GUIDE_TERMS, w):
+        if not (math.isfinite(v) and v >= 0):
+            raise ValueError(f"guide['weights'][{k!r}] = {v}: a weight is a finite number >= 0")
+    return w
+
+
+def _one_list_for_all(rs):
+    """a non-empty list whose entries are restraints themselves, (i, j, lo, hi, weight), not lists of restraints"""
+    return len(rs) > 0 and all(isinstance(r, (list, tuple)) and len(r) == 5 and not isinstance(r[0], (list, tuple)) for r in rs)
+
+
+def _guide_restraints(restraints, B):
+    """None, one list of (i, j, lo, hi, weight) for every sample, or a list of B such lists -> B lists"""
+    if restraints is None:
+        return [[] for _ in range(B)]
+    rs = list(restraints)
+    if not rs:
+        return [[] for _ in range(B)]
+    if _one_list_for_all(rs):
+        return [rs for _ in range(B)]
+    if len(rs) != B:
+        raise ValueError(f"guide['restraints']: expected one list of (i, j, lo, hi, weight) or one list per sample ({B}), got {len(rs)} lists")
+    return [list(r) for r in rs]
+
+
+def make_guide(guide, B, L, generate_mask=None, res_mask=None):
+    """sample()'s `guide` dict, validated and packed on the host: None -> None, else a dict of CPU tensors at the caller's [B, L]:
+    params fp32 [16] (pf_guidance_args.params), hotspots uint8 [B, L] or None, pair_idx int32 [B, 64, 2], pair_par fp32 [B, 64, 3]
+    (lo, hi, weight; weight 0 pads).  generate_mask / res_mask (bool [B, L]), when given, are what a hot spot and a restraint index
+    are checked against.  ValueError with the offending value: a hot spot on a generated residue, an index outside the sample,
+    lo > hi, a negative weight, a power outside {0, 1, 2}, t_on >= 1, more than 64 restraints of one sample."""
+    if guide is None:
+        return None
+    if not isinstance(guide, dict):
+        raise ValueError(f"guide: expected None or a dict, got {type(guide).__name__}")
+    for k in guide:
+        if k not in GUIDE_DEFAULTS:
+            raise ValueError(f"guide: unknown entry {k!r}; the entries are {tuple(GUIDE_DEFAULTS)}")
+    g = {**GUIDE_DEFAULTS, **guide}
+    gen = None if generate_mask is None else torch.as_tensor(generate_mask).detach().cpu().bool()
+    resm = None if res_mask is None else torch.as_tensor(res_mask).detach().cpu().bool()
+    vals = {k: float(g[k]) for k in _GUIDE_SLOTS}
+    for k in ("r_receptor", "r_self", "r_hotspot", "bond_tol", "scale", "max_shift", "min_sep"):
+        if not (math.isfinite(vals[k]) and vals[k] >= 0):
+            raise ValueError(f"guide[{k!r}] = {g[k]!r}: expected a finite number >= 0")
+    if not (math.isfinite(vals["beta"]) and vals["beta"] > 0):
+        raise ValueError(f"guide['beta'] = {g['beta']!r}: expected a finite number > 0")
+    if g["power"] not in (0, 1, 2) or isinstance(g["power"], bool):
+        raise ValueError(f"guide['power'] = {g['power']!r}: expected 0, 1 or 2")
+    if int(g["min_sep"]) != g["min_sep"]:
+        raise ValueError(f"guide['min_sep'] = {g['min_sep']!r}: expected an integer")
+    if not 0.0 <= vals["t_on"] < 1.0:
+        raise ValueError(f"guide['t_on'] = {g['t_on']!r}: expected 0 <= t_on < 1")
+    params = np.zeros(_capi.GUIDE_NPARAMS, dtype=np.float32)
+    params[:4] = _guide_weights(g["weights"])
+    params[4:4 + len(_GUIDE_SLOTS)] = [vals[k] for k in _GUIDE_SLOTS]
+    hot = None
+    if g["hotspots"] is not None:
+        h = torch.as_tensor(g["hotspots"]).detach().cpu()
+        if h.dtype != torch.bool or tuple(h.shape) not in ((L,), (B, L)):
+            raise ValueError(f"guide['hotspots']: expected bool [{L}] or [{B}, {L}], got {h.dtype} {tuple(h.shape)}")
+        h = h.expand(B, L)
+        for name, bad in (("a generated residue", gen), ("a residue outside the sample", None if resm is None else ~resm)):
+            if bad is not None and bool((h & bad).any()):
+                b, l = (h & bad).nonzero()[0].tolist()
+                raise ValueError(f"guide['hotspots']: sample {b}, residue {l} is {name}; a hot spot is a context residue")
+        hot = torch.from_numpy(np.ascontiguousarray(h.numpy().astype(np.uint8)))
+    n_max = _capi.GUIDE_MAX_PAIRS
+    idx, par = np.zeros((B, n_max, 2), dtype=np.int32), np.zeros((B, n_max, 3), dtype=np.float32)
+    for b, rs in enumerate(_guide_restraints(g["restraints"], B)):
+        if len(rs) > n_max:
+            raise ValueError(f"guide['restraints']: sample {b} has {len(rs)} restraints; at most {n_max}")
+        for p, r in enumerate(rs):
+            if len(r) != 5:
+                raise ValueError(f"guide['restraints']: sample {b}, restraint {p}: expected (i, j, lo, hi, weight), got {tuple(r)!r}")
+            if int(r[0]) != r[0] or int(r[1]) != r[1]:
+                raise ValueError(f"guide['restraints']: sample {b}, restraint {p}: residue indices must be integers, got {r[0]!r}, {r[1]!r}")
+            i, j, lo, hi, w = int(r[0]), int(r[1]), float(r[2]), float(r[3]), float(r[4])
+            for v in (i, j):
+                if not 0 <= v < L or (resm is not None and not bool(resm[b, v])):
+                    raise ValueError(f"guide['restraints']: sample {b}, restraint {p}: residue index {v} lies outside the sample")
+            if not (math.isfinite(lo) and math.isfinite(hi)) or lo > hi:
+                raise ValueError(f"guide['restraints']: sample {b}, restraint {p}: lo = {lo} > hi = {hi}")
+            if not (math.isfinite(w) and w >= 0):
+                raise ValueError(f"guide['restraints']: sample {b}, restraint {p}: weight {w}: a weight is a finite number >= 0")
+            idx[b, p], par[b, p] = (i, j), (lo, hi, w)
+    return {"params": torch.from_numpy(params), "hotspots": hot, "pair_idx": torch.from_numpy(idx), "pair_par": torch.from_numpy(par)}
+
+
+def fit_guide(guide, L0, Lk, idx=None):
+    """The packed guidance (make_guide) of the samples `idx` (None: all) with the residue axis of the hot-spot plane cut or padded
+    from L0 to Lk (no hot spot on the padding).  Restraints carry residue INDICES: padding is appended at the end, so they stay."""
+    if guide is None:
+        return None
+    from .buckets import _fit, _rows
+    out = dict(guide)
+    if guide["hotspots"] is not None:
+        h = guide["hotspots"] if idx is None else _rows(guide["hotspots"], idx)
+        out["hotspots"] = _fit(h, L0, Lk, 1, 0)
+    if idx is not None:
+        out["pair_idx"], out["pair_par"] = _rows(guide["pair_idx"], idx), _rows(guide["pair_par"], idx)
+    return out
+
+
+def shard_guide(guide, lo, hi, total):
+    """sample()'s `guide` dict with its per-sample entries (hotspots [total, L], one restraint list per sample) cut to the shard [lo, hi)"""
+    if not isinstance(guide, dict):
+        return guide
+    out = dict(guide)
+    h = out.get("hotspots")
+    if h is not None and torch.as_tensor(h).dim() == 2 and torch.as_tensor(h).shape[0] == total:
+        out["hotspots"] = torch.as_tensor(h)[lo:hi]
+    r = out.get("restraints")
+    if r is not None and len(r) == total and not _one_list_for_all(list(r)):
+        out["restraints"] = list(r)[lo:hi]
+    return out
+
+
+class DeviceSampler:
+    """Owned by its engine (DenoiseEngine.sampler caches one per (num_steps, flags, cond, guide)): trajectory buffers and the captured
+    graphs are reused by the next sample() call; set_seed() / set_grid() / set_context() / set_cond() / set_guide() / init_state() are
+    what a call changes."""
+
+    def __init__(self, engine, num_steps, flags=(True, True, True), first_sample=0, seed=0, cond=False, guide=False):
         self.eng = engine
         self.lib = engine.lib
         self.N = num_steps
@@ -251,6 +393,24 @@ class DeviceSampler:
             self.start_rot, self.start_trans, self.start_ang = e(rows, 9), e(rows, 3), e(rows, 5)
             self.start_seq = e(rows, dt=torch.int64)
             self.cargs = _capi.SamplerCondArgs()
+        # guided calls (pf_guidance_fwd between the network and the step kernel): the parameters, the hot-spot plane, the restraint
+        # list, the guided copy of the prediction and the per-step records live in buffers THIS sampler owns; the step kernel reads
+        # the guided copy.  A call only rewrites the buffers' contents (set_guide), so the captured graphs keep serving.
+        self.guide = bool(guide)
+        if self.guide:
+            n_pairs = _capi.GUIDE_MAX_PAIRS
+            self.g_params, self.g_hot = e(_capi.GUIDE_NPARAMS), e(rows, dt=torch.uint8)
+            self.g_pair_idx, self.g_pair_par = e(B, n_pairs, 2, dt=torch.int32), e(B, n_pairs, 3)
+            self.guided_trans = e(rows, 3)
+            self.g_energy, self.g_shift = e(num_steps, B, _capi.GUIDE_NTERMS), e(num_steps, B)
+            self.g_error = e(B, dt=torch.int32)
+            g = self.gargs = _capi.GuidanceArgs()
+            g.pred_trans, g.trans1, g.gen_mask, g.res_mask = engine.trans.data_ptr(), a.trans1, a.gen_mask, a.res_mask
+            g.pair_idx, g.pair_par, g.params = self.g_pair_idx.data_ptr(), self.g_pair_par.data_ptr(), self.g_params.data_ptr()
+            g.ts, g.step, g.num_steps = a.ts, a.step, num_steps
+            g.guided_trans, g.energy, g.shift_max = self.guided_trans.data_ptr(), self.g_energy.data_ptr(), self.g_shift.data_ptr()
+            g.error, g.B, g.L, g.sample_bb = self.g_error.data_ptr(), B, L, a.sample_bb
+            a.pred_trans = self.guided_trans.data_ptr()
         self.graph = None
         self.graph_k = None
         self._graph_key = None
@@ -279,6 +439,8 @@ class DeviceSampler:
         key = (eng.plan_version, eng.active_rows, eng.padded, self.args.expo)
         if self.cond:                                   # which constraint planes the step kernel was launched with (NULL or the buffer)
             key += (self.cargs.res_flags, self.cargs.aa_allowed)
+        if self.guide:                                  # ... and whether the guidance kernel was launched with a hot-spot plane
+            key += (self.gargs.hotspots,)
         return key
 
     def set_grid(self, grid):
@@ -307,6 +469,31 @@ class DeviceSampler:
                 buf.copy_((nat if src is None else src).reshape(buf.shape))
         c.start_rot, c.start_trans = self.start_rot.data_ptr(), self.start_trans.data_ptr()
         c.start_ang, c.start_seq = self.start_ang.data_ptr(), self.start_seq.data_ptr()
+
+    def set_guide(self, guide):
+        """The call's guidance (sampler.make_guide, hot-spot plane padded to the engine's length) into the owned buffers; the
+        per-step records start from zero."""
+        assert self.guide, "a sampler built without guide=True has no guidance buffers"
+        B, rows = self.eng.B, self.eng.rows
+        assert guide["pair_idx"].shape == self.g_pair_idx.shape and guide["pair_par"].shape == self.g_pair_par.shape, guide["pair_idx"].shape
+        self.g_params.copy_(guide["params"])
+        self.g_pair_idx.copy_(guide["pair_idx"])
+        self.g_pair_par.copy_(guide["pair_par"])
+        hot = guide.get("hotspots")
+        if hot is not None:
+            self.g_hot.copy_(hot.reshape(rows))
+        self.gargs.hotspots = self.g_hot.data_ptr() if hot is not None else None
+        self.g_energy.zero_()
+        self.g_shift.zero_()
+        self.g_error.zero_()
+
+    def guidance(self):
+        """The records of a guided run as CPU tensors: energy [num_steps, B, 5] (the terms of every step's UNGUIDED prediction, in the
+        order of GUIDE_TERMS), shift_max [num_steps, B].  Raises if the kernel refused a restraint index."""
+        err = self.g_error.cpu()
+        if bool((err != 0).any()):
+            raise _capi.PepflowHipError(f"pf_guidance_fwd refused a restraint index outside the sample (samples {err.nonzero().flatten().tolist()})")
+        return {"energy": self.g_energy.cpu(), "shift_max": self.g_shift.cpu(), "terms": GUIDE_TERMS}
 
     def set_context(self, R1, x1, ang1, seq1, gen_mask):
         rows = self.eng.rows
@@ -343,6 +530,10 @@ class DeviceSampler:
 
     def _one_step(self):
         self.eng.run(concurrent=self.CONCURRENT)
+        if self.guide:                                  # the guided copy of the translation prediction: what the step kernel reads
+            self.gargs.res_flags = self.cargs.res_flags if self.cond else None
+            rc = self.lib.pf_guidance_fwd(C.byref(self.gargs), _capi.stream_ptr())
+            _capi.check(rc, "pf_guidance_fwd")
         if self.cond:
             rc = self.lib.pf_sampler_step_cond(C.byref(self.args), C.byref(self.cargs), _capi.stream_ptr())
             _capi.check(rc, "pf_sampler_step_cond")
