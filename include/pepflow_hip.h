@@ -1136,6 +1136,62 @@ typedef struct {
 } pf_sasa_args;
 int pf_sasa_fwd(const pf_sasa_args* a, pf_stream_t stream);
 
+/* ---- cavity detection (ABI 65, added entry points) ----------------------------------------------------------------------------
+ * pf_cavity_fwd: a LIGSITE-style buriedness scan (Hendlich et al. 1997) of B structures of N residues over a regular grid, the
+ * connected cavities of the buried free points, their ranking and their lining residues (csrc/cavity.hip).  pos [B,N,n_atoms,3]
+ * in the package's heavy-atom order, n_atoms >= 14, slots 0 .. min(n_atoms,15)-1 are read; atom_mask [B,N,n_atoms]; aa [B,N];
+ * radius [21,15] by (type, slot); origin [B,3]; nx, ny, nz and h are common to the batch, G = nx * ny * nz.  The contract:
+ *   Point        linear index i = (ix * ny + iy) * nz + iz; its coordinate is g = origin + (float)index * h per axis, in fp32.
+ *   Occupied     for some atom a whose atom_mask is set: ((dx*dx + dy*dy) + dz*dz) <= R_a*R_a with dx = gx - ax, dy = gy - ay,
+ *                dz = gz - az, in fp32, in exactly that order, no contraction; R_a = radius[type, slot] + probe, added in fp32.
+ *   Buriedness   of a free point, 0..7: the number of the 7 lines through it (the 3 axes, the 4 body diagonals) on which an occupied
+ *                point lies within n_axis (axes) / n_diag (diagonals) grid steps in BOTH senses.  A walk ends at the grid's edge:
+ *                outside the grid is free.  The caller computes n_axis = floor(max_ray / h), n_diag = floor(max_ray / (h sqrt 3)) in
+ *                float64.  An occupied point gets 255.
+ *   Cavity point a free point with buriedness >= min_buried (1..7).
+ *   Cavities     the connected components of the cavity points under connectivity 6 (faces) or 26 (faces, edges, corners).
+ *                Components of fewer than min_points points are dropped; the rest are ranked by size descending, ties by the
+ *                smallest linear index of a member; the first max_cavities (1..PF_CAVITY_MAX_OUT) are reported, K = max_cavities.
+ *   occupied [B,G]      1 / 0;                 buried [B,G]    the buriedness, 255 where occupied;
+ *   label [B,G]         rank of the point's cavity among the reported ones, or -1;
+ *   n_found [B]         kept components before the max_cavities cut;
+ *   size [B,K]          points of the cavity;
+ *   center [B,K,3]      mean of the members' coordinates g, accumulated in double, rounded once;
+ *   mean_buried [B,K]   mean buriedness of the members, likewise;
+ *   lining [B,K,N]      1 when the residue has an atom (atom_mask set) within r_lining of a member point: ((dx*dx + dy*dy) + dz*dz)
+ *                       <= r_lining*r_lining, the same fp32 rule;
+ *   rows k >= min(n_found, K) of size, center, mean_buried and lining are zero.
+ *   status [1]          0, or a bit set by a device loop that ran out of its bound (1: a path to a root, 2: the retries of a link,
+ *                       4: the list of components); the outputs are then not valid.  Every device loop is bounded by the arguments
+ *                       (steps of a walk, the grid, G); none waits for another thread.
+ * work: B x pf_cavity_work_bytes(nx, ny, nz) bytes, no initialisation needed.  A fixed sequence of launches and memset nodes on the
+ * caller's stream, integer atomics only, nothing read back by the host: the results are bit-identical from run to run and do not
+ * depend on the other structures.  N > PF_CAVITY_MAX_N, G > PF_CAVITY_MAX_POINTS or B > 65535 -> PF_E_TOOLARGE. */
+#define PF_CAVITY_MAX_N 4096
+#define PF_CAVITY_MAX_POINTS 2097152    /* 128^3 */
+#define PF_CAVITY_MAX_OUT 32
+#define PF_CAVITY_SLOTS 15
+typedef struct {
+    const float* pos;                   /* [B,N,n_atoms,3] */
+    const unsigned char* atom_mask;     /* [B,N,n_atoms] */
+    const int64_t* aa;                  /* [B,N] */
+    const float* radius;                /* [21,15] */
+    const float* origin;                /* [B,3] */
+    void* work;                         /* B x pf_cavity_work_bytes(nx, ny, nz) bytes */
+    unsigned char* occupied; unsigned char* buried;     /* [B,G] */
+    int* label;                         /* [B,G] */
+    int* n_found;                       /* [B] */
+    int* size;                          /* [B,K] */
+    float* center;                      /* [B,K,3] */
+    float* mean_buried;                 /* [B,K] */
+    unsigned char* lining;              /* [B,K,N] */
+    int* status;                        /* [1] */
+    int B, N, n_atoms, nx, ny, nz, n_axis, n_diag, min_buried, connectivity, min_points, max_cavities;
+    float h, probe, r_lining;
+} pf_cavity_args;
+int pf_cavity_fwd(const pf_cavity_args* a, pf_stream_t stream);
+int pf_cavity_work_bytes(int nx, int ny, int nz);   /* scratch bytes per structure (-1 for a dimension < 1 or G > PF_CAVITY_MAX_POINTS) */
+
 /* ---- torsion angles and side-chain packing (ABI 64, added entry points) -------------------------------------------------------
  * pf_torsions_fwd: omega, phi, psi, psi_o (N, CA, C, O) and chi1-chi4 of B structures of N residues; the conventions are listed in
  * csrc/torsions.hip.  pos [B,N,n_atoms,3] in the package's heavy-atom order, n_atoms >= 14, slots 0..13 are read; atom_mask

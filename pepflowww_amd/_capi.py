@@ -225,6 +225,14 @@ class SasaArgs(C.Structure):
                 ("n_points", _i), ("probe_radius", C.c_float)]
 
 
+class CavityArgs(C.Structure):
+    _fields_ = [("pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("radius", _fp), ("origin", _fp), ("work", _fp), ("occupied", _fp),
+                ("buried", _fp), ("label", _fp), ("n_found", _fp), ("size", _fp), ("center", _fp), ("mean_buried", _fp),
+                ("lining", _fp), ("status", _fp), ("B", _i), ("N", _i), ("n_atoms", _i), ("nx", _i), ("ny", _i), ("nz", _i),
+                ("n_axis", _i), ("n_diag", _i), ("min_buried", _i), ("connectivity", _i), ("min_points", _i), ("max_cavities", _i),
+                ("h", C.c_float), ("probe", C.c_float), ("r_lining", C.c_float)]
+
+
 class TorsionsArgs(C.Structure):
     _fields_ = [("pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("residue_index", _fp), ("chi_atoms", _fp), ("angles", _fp),
                 ("defined", _fp), ("B", _i), ("N", _i), ("n_atoms", _i)]
@@ -380,6 +388,8 @@ _SIGNATURES = {
     "pf_tm_align_lds_bytes": ([_i], _i),
     "pf_violations_fwd": ([C.POINTER(ViolationsArgs), _fp], _i),
     "pf_sasa_fwd": ([C.POINTER(SasaArgs), _fp], _i),
+    "pf_cavity_fwd": ([C.POINTER(CavityArgs), _fp], _i),
+    "pf_cavity_work_bytes": ([_i, _i, _i], _i),
     "pf_torsions_fwd": ([C.POINTER(TorsionsArgs), _fp], _i),
     "pf_sidechain_compare_fwd": ([C.POINTER(SidechainCompareArgs), _fp], _i),
     "pf_lddt_fwd": ([C.POINTER(LddtArgs), _fp], _i),

@@ -6,6 +6,7 @@ Input families, one binding path each:
                     superpose_rmsd), tm_score, tm_align and their pairwise_* matrices (`_within_groups`, `_mirrored`);
   heavy-atom structures   pos [B,N,A,3], atom_mask [B,N,A] and per-residue [B,N] tensors -- `_structure`: structural_violations, sasa,
                     torsion_angles, interface_energy and each side of sidechain_compare (dssp reads the same pos with a residue mask);
+                    cavity_scan (pf_cavity_fwd: buriedness scan, cavities and lining residues of whole receptors, N <= 4096) too;
   both at once      two heavy-atom structure sets and a work list -- `_structure_pairs`: lddt (pf_lddt_fwd, the values of OpenFold's
                     lddt / lddt_ca, openfold/utils/loss.py:382-458) and interface_contacts (pf_contacts_fwd), which dockq combines
                     with `superpose` into Fnat, iRMSD, LRMSD and DockQ.
@@ -559,6 +560,123 @@ def sasa(pos, atom_mask, aa, query=None, group=None, probe_radius=1.4, n_points=
         for v in out.values():
             v.zero_()
     return out
+
+
+CAVITY_MAX_N, CAVITY_MAX_POINTS, CAVITY_MAX_OUT = 4096, 128 ** 3, 32
+CAVITY_DEFAULTS = {"probe": 1.4, "max_ray": 12.0, "min_buried": 5, "connectivity": 6, "min_points": 8, "max_cavities": 8,
+                   "r_lining": 4.5}
+CAVITY_STATUS = {1: "a path to a root", 2: "the retries of a link", 4: "the list of components"}
+
+
+def cavity_grid(pos, atom_mask, h=1.0, margin=8.0):
+    """The grid of `cavity_scan` around structures: the bounding box of the atoms of pos [B,N,A,3] with atom_mask [B,N,A] set, padded
+    by `margin` on every side, its lower corner snapped down to a multiple of h.  A host computation (float64, the tensors are read
+    back).  -> (origin [B,3] float32 CPU tensor, (nx, ny, nz)): the dimensions are those of the largest structure; a structure without
+    atoms gets the origin 0."""
+    h, margin = float(h), float(margin)
+    if not (h > 0.0 and math.isfinite(h)) or not (margin >= 0.0 and math.isfinite(margin)):
+        raise ValueError(f"h must be > 0 and margin >= 0, got {h}, {margin}")
+    if pos.dim() != 4 or pos.shape[3] != 3 or tuple(atom_mask.shape) != tuple(pos.shape[:3]):
+        raise ValueError(f"pos must be [B,N,A,3] and atom_mask [B,N,A], got {tuple(pos.shape)}, {tuple(atom_mask.shape)}")
+    B = pos.shape[0]
+    p, m = pos.detach().cpu().double().reshape(B, -1, 3), atom_mask.detach().cpu().bool().reshape(B, -1)
+    origin, dims = torch.zeros(B, 3, dtype=torch.float64), [1, 1, 1]
+    for b in range(B):
+        if not m[b].any():
+            continue
+        x = p[b][m[b]]
+        lo = torch.floor((x.min(0).values - margin) / h)
+        hi = torch.ceil((x.max(0).values + margin) / h)
+        origin[b] = lo * h
+        dims = [max(d, int(n)) for d, n in zip(dims, (hi - lo + 1).tolist())]
+    return origin.to(torch.float32), tuple(dims)
+
+
+def _cavity_params(h, params):
+    """the scan's parameters, checked (ValueError) -> (dict with the defaults filled in, n_axis, n_diag)"""
+    unknown = set(params) - set(CAVITY_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown cavity scan parameters {sorted(unknown)}; known: {sorted(CAVITY_DEFAULTS)}")
+    p = {**CAVITY_DEFAULTS, **params}
+    if not (h > 0.0 and h < 1e6):
+        raise ValueError(f"h must be > 0, got {h}")
+    for k in ("probe", "max_ray", "r_lining"):
+        p[k] = float(p[k])
+        if not 0.0 <= p[k] < 1e6:
+            raise ValueError(f"{k} must be >= 0, got {p[k]}")
+    for k in ("min_buried", "connectivity", "min_points", "max_cavities"):
+        if not isinstance(p[k], int) or isinstance(p[k], bool):
+            raise ValueError(f"{k} must be an integer, got {p[k]!r}")
+    if not 1 <= p["min_buried"] <= 7:
+        raise ValueError(f"min_buried must be in 1..7, got {p['min_buried']}")
+    if p["connectivity"] not in (6, 26):
+        raise ValueError(f"connectivity must be 6 or 26, got {p['connectivity']}")
+    if p["min_points"] < 1 or not 1 <= p["max_cavities"] <= CAVITY_MAX_OUT:
+        raise ValueError(f"min_points must be >= 1 and max_cavities in 1..{CAVITY_MAX_OUT}, got {p['min_points']}, {p['max_cavities']}")
+    return p, int(math.floor(p["max_ray"] / h)), int(math.floor(p["max_ray"] / (h * math.sqrt(3.0))))
+
+
+def cavity_scan(pos, atom_mask, aa, origin, dims, h=1.0, radius=None, check=True, **params):
+    """pf_cavity_fwd: a LIGSITE-style buriedness scan (Hendlich et al. 1997) over a grid around heavy-atom structures, the connected
+    cavities of the buried free points, their ranking and lining residues; the definitions are in include/pepflow_hip.h and
+    csrc/cavity.hip, tests/cavity_oracle.py restates them.  Not checked against the LIGSITE program or fpocket; defaults untuned.
+
+    pos [B,N,A,3] heavy atoms in the package's order (A >= 14, slots 0 .. min(A,15)-1 are read), atom_mask [B,N,A], aa [B,N], all on
+    the device; N <= 4096.  origin [B,3] and dims = (nx, ny, nz) (`cavity_grid`), nx * ny * nz <= 128^3, spacing h; point (ix, iy, iz)
+    has the linear index (ix * ny + iy) * nz + iz and lies at origin + index * h.  radius [21,15] (default `sasa_radius_table`).
+    params: CAVITY_DEFAULTS (probe, max_ray, min_buried, connectivity, min_points, max_cavities = K, r_lining).
+    -> dict of device tensors: occupied [B,G] bool, buried [B,G] uint8 (0..7, 255 where occupied), label [B,G] int32 (rank or -1),
+    n_found [B] int32, size [B,K] int32, center [B,K,3], mean_buried [B,K], lining [B,K,N] bool, status [1] int32.
+    `check` reads the status word back and raises PepflowHipError when a device loop ran out of its bound; it is skipped while the
+    stream is being captured (the call makes no host read then: check out["status"] after a replay)."""
+    h = float(h)
+    p, n_axis, n_diag = _cavity_params(h, params)
+    try:
+        nx, ny, nz = (int(d) for d in dims)
+    except (TypeError, ValueError):
+        raise ValueError(f"dims must be three integers, got {dims!r}") from None
+    if min(nx, ny, nz) < 1 or nx * ny * nz > CAVITY_MAX_POINTS:
+        raise ValueError(f"dims must be >= 1 with at most {CAVITY_MAX_POINTS} points in all, got {(nx, ny, nz)}")
+    dev, (B, N, A), pos, atom_mask, (aa,) = _structure(pos, atom_mask, (("aa", aa, torch.int64),), max_n=CAVITY_MAX_N)
+    if not isinstance(origin, torch.Tensor) or tuple(origin.shape) != (B, 3):
+        raise ValueError(f"origin must be a [B,3] = {(B, 3)} tensor, got {tuple(getattr(origin, 'shape', ()))}")
+    if radius is not None and tuple(radius.shape) != (21, SASA_SLOTS):
+        raise ValueError(f"radius must be [21,{SASA_SLOTS}], got {tuple(radius.shape)}")
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    origin = _f32(origin, dev)
+    radius = _table("sasa_radius", dev, sasa_radius_table) if radius is None else _f32(radius, dev)
+    a = _capi.CavityArgs()
+    _bind_in(a, pos=pos, atom_mask=atom_mask, aa=aa, radius=radius, origin=origin)
+    G, K = nx * ny * nz, p["max_cavities"]
+    new = lambda dt, *shape: torch.empty(*shape, dtype=dt, device=dev)  # noqa: E731
+    out = {"occupied": new(torch.uint8, B, G), "buried": new(torch.uint8, B, G), "label": new(torch.int32, B, G),
+           "n_found": new(torch.int32, B), "size": new(torch.int32, B, K), "center": new(torch.float32, B, K, 3),
+           "mean_buried": new(torch.float32, B, K), "lining": new(torch.uint8, B, K, N),
+           "status": torch.zeros(1, dtype=torch.int32, device=dev)}
+    _bind_out(a, out)
+    a.B, a.N, a.n_atoms, a.nx, a.ny, a.nz, a.n_axis, a.n_diag = B, N, A, nx, ny, nz, n_axis, n_diag
+    a.min_buried, a.connectivity, a.min_points, a.max_cavities = p["min_buried"], p["connectivity"], p["min_points"], K
+    a.h, a.probe, a.r_lining = h, p["probe"], p["r_lining"]
+    if B:
+        lib = _capi.load()
+        work = new(torch.uint8, B * lib.pf_cavity_work_bytes(nx, ny, nz))
+        a.work = work.data_ptr()
+        _capi.check(lib.pf_cavity_fwd(C.byref(a), _capi.stream_ptr()), "pf_cavity_fwd")
+        if N == 0:
+            out["lining"].zero_()
+        if check and not torch.cuda.is_current_stream_capturing():
+            cavity_check(out["status"])
+    _as_bool(out, "occupied", "lining")
+    return out
+
+
+def cavity_check(status):
+    """raises PepflowHipError when `cavity_scan`'s status word says that a device loop ran out of its bound (a host read)"""
+    s = int(status.item())
+    if s:
+        what = ", ".join(v for k, v in CAVITY_STATUS.items() if s & k)
+        raise _capi.PepflowHipError(f"pf_cavity_fwd: a device loop exhausted its bound ({what}; status {s}); the outputs are not valid")
 
 
 TORSION_NAMES = ("omega", "phi", "psi", "psi_o", "chi1", "chi2", "chi3", "chi4")
