@@ -152,6 +152,7 @@ typedef struct {
     float* s_out;              /* [B*L,128] */
     int B, L;
     int single_pass;           /* 1 = f16 precision mode: one f16 MFMA per product (hi weight planes only) */
+    void* k_frag_s;            /* optional (appended, additive to ABI 65): the rows of s_out also as block 0's shared k fragments (pf_ipa_attn_args.k_frag_s) */
 } pf_input_mixer_args;
 int pf_input_mixer_fwd(const pf_input_mixer_args* a, pf_stream_t stream);
 
@@ -235,6 +236,13 @@ typedef struct {
      * (engine.fold_keys_into_queries: weights only) the k operand of the first product is the row of s_in itself: the kernel writes its
      * fragments from s_in and passes over the eight k tiles of the packed projection (whose rows are then never multiplied). */
     int k_from_s;
+    /* optional (with k_from_s, fp32 operands, without fused_pair; appended, additive to ABI 65): the keys as hi | lo f16 operand fragments, ONE copy per sample
+     * shared by its eight heads, [B][ceil(L / 16) tiles][8 KiB] f16: per 16-key tile and 32-channel K-step s 2 KiB (hi KiB, lo KiB), in
+     * a KiB lane (key r, g) holds 16 bytes: halves 0..3 = channels 32 s + 4 g .. + 3, halves 4..7 = channels 32 s + 16 + 4 g .. + 3;
+     * hi = f16(v), lo = f16(v - hi), unscaled.  Written by the producer of s_in (pf_input_mixer_args.k_frag_s / pf_node_tfmr_args.k_frag_s);
+     * rows at or beyond a sample's key end only have to be finite.  NULL: the launch forms them itself (one small kernel in front,
+     * into att_vt); the results are the same bytes either way.  Ignored by every other form. */
+    const void* k_frag_s;
 } pf_ipa_attn_args;
 int pf_ipa_attn_fwd(const pf_ipa_attn_args* a, pf_stream_t stream);
 /* 1 when pf_ipa_attn_fwd would run the projection-inside form (s_in) at this length (fp32 operands: f16_mode = 0; f16 operand
@@ -332,6 +340,10 @@ typedef struct {
      * without a marked group is skipped (nothing of it is written).  The sampler marks the groups that hold a generated residue in
      * the LAST block of a step: the predictions of context residues are replaced by the context anyway (flow_model.py:291-311). */
     const int* row_on;
+    /* optional (last == 1; appended, additive to ABI 65; ignored by the training forward, i.e. with dump): the rows of s_out also as the next attention's shared
+     * k fragments (pf_ipa_attn_args.k_frag_s, [B][ceil(L / 16)][8 KiB] f16), from the registers that hold them; skipped tiles keep what
+     * they held */
+    void* k_frag_s;
 } pf_node_tfmr_args;
 int pf_node_tfmr_fwd(const pf_node_tfmr_args* a, pf_stream_t stream);
 

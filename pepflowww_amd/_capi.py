@@ -45,13 +45,13 @@ class IpaAttnArgs(C.Structure):
                 ("trans", _fp), ("mask", _fp), ("w_b", _fp), ("b_b", _fp), ("w_dz", _fp), ("b_dz", _fp),
                 ("head_w", _fp), ("feats", _fp), ("B", _i), ("L", _i), ("bias", _fp), ("p_out", _fp),
                 ("variant", _i), ("att_qk", _fp), ("att_vt", _fp), ("att_mode", _i), ("head_group", _i), ("key_end", _fp), ("z_f16", _i), ("dz", _fp), ("dz_f16", _i), ("fused_pair", _i),
-                ("s_in", _fp), ("proj_w_f16", _fp), ("proj_bias", _fp), ("k_frag", _fp), ("k_from_s", _i)]
+                ("s_in", _fp), ("proj_w_f16", _fp), ("proj_bias", _fp), ("k_frag", _fp), ("k_from_s", _i), ("k_frag_s", _fp)]
 
 
 class InputMixerArgs(C.Structure):
     _fields_ = [("node_embed", _fp), ("seq_table", _fp), ("seqs", _fp), ("t", _fp), ("time_freq", _fp), ("ang_freq", _fp),
                 ("angles", _fp), ("w0_f16", _fp), ("b0", _fp), ("w2_f16", _fp), ("b2", _fp), ("mask", _fp), ("rot", _fp),
-                ("quat", _fp), ("s_out", _fp), ("B", _i), ("L", _i), ("single_pass", _i)]
+                ("quat", _fp), ("s_out", _fp), ("B", _i), ("L", _i), ("single_pass", _i), ("k_frag_s", _fp)]
 
 
 class SeqAttnArgs(C.Structure):
@@ -178,7 +178,7 @@ class NodeTfmrArgs(C.Structure):
                 ("b_bb", _fp), ("s_out", _fp), ("quat_in", _fp), ("rot_in", _fp), ("trans_in", _fp),
                 ("quat_out", _fp), ("rot_out", _fp), ("trans_out", _fp), ("has_et", _i),
                 ("w_init_f16", _fp), ("b_init", _fp), ("w_pre_f16", _fp), ("b_pre", _fp), ("pre", _fp), ("B", _i), ("L", _i),
-                ("h_w", (_fp * 3) * 2), ("h_b", (_fp * 3) * 2), ("logits_out", _fp), ("ang_out", _fp), ("single_pass", _i), ("key_end", _fp), ("dump", _fp * 11), ("row_on", _fp)]
+                ("h_w", (_fp * 3) * 2), ("h_b", (_fp * 3) * 2), ("logits_out", _fp), ("ang_out", _fp), ("single_pass", _i), ("key_end", _fp), ("dump", _fp * 11), ("row_on", _fp), ("k_frag_s", _fp)]
 
 
 class SuperposeArgs(C.Structure):

@@ -252,6 +252,34 @@ __device__ __forceinline__ void split4(const float (&v)[4], half4& hi, half4& lo
 }
 __device__ __forceinline__ float join(f32x4 m, f32x4 c, int e) { return m[e] + c[e] * PF_LO_INV; }
 
+// hi | lo split with the hi plane DEFINED by the packed registers the MFMA reads.  hipcc may select f16(x) twice -- inside the packed
+// conversion that builds the operand vector (v_cvt_pk_f16_f32 of the fp32 value) and again for the scalar that feeds lo, and when x
+// is a product or a sum it folds that second one into v_fma_mixlo_f16, which rounds ONCE from the exact result.  At an fp32 value
+// that lies exactly between two f16 numbers the two selections differ by one f16 ulp and hi + lo is off by that ulp: with
+// -fno-slp-vectorize the fused form did exactly that to a probability of 0.0625 - 2^-16 (one query row of 8192, 1e-4 against the
+// oracle; the packed build had happened to extract lo's operand from the packed registers).  The empty asm makes the vector opaque:
+// what lo is computed from is what the MFMA multiplies.  No instruction.
+template <class V> __device__ __forceinline__ void pf_pin(V& v) { asm("" : "+v"(v)); }
+
+// ---- the node state as the k operand of the IPA score kernel (pf_ipa_attn_args.k_frag_s; ipa_split.hip: proj_head) ----
+// A sample's keys as hi | lo f16 operand fragments, UNSCALED (hi = f16(v), lo = f16(v - hi): not split4), 8 KiB per 16-key tile:
+// 32-channel K-step s = 2 KiB (hi KiB | lo KiB), lane (key r, g) of a KiB holds 16 bytes -- halves 0..3 = channels 32 s + 4 g .. + 3,
+// halves 4..7 = channels 32 s + 16 + 4 g .. + 3.  This stores the four channels 16 t8 + 4 g .. + 3 of key row i (row within its
+// sample) into the sample's buffer `kf`: written by whoever produces s (node_track.hip) or, for a caller without a producer, by
+// ipa_kfrag_kernel -- ONE statement of the layout and of the conversion, so the fragments are the same bytes wherever they come from.
+__device__ __forceinline__ void pf_kfrag_put(_Float16* kf, int i, int t8, int g, const float (&v)[4]) {
+    half4 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) hi[e] = (_Float16)v[e];
+    pf_pin(hi);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) lo[e] = (_Float16)(v[e] - (float)hi[e]);
+    _Float16* d = kf + (size_t)(i >> 4) * 4096 + (t8 >> 1) * 1024 + ((i & 15) + 16 * g) * 8 + (t8 & 1) * 4;
+    *reinterpret_cast<half4*>(d) = hi;
+    *reinterpret_cast<half4*>(d + 512) = lo;
+}
+constexpr int PF_KFRAG_TILE_B = 8192;          // bytes of one 16-key tile of such a buffer
+
 // Weight stream of one wave for a 16-row activation tile: WT tiles of 16 output features, D K-steps (of 32)
 // in flight.  Computed TRANSPOSED (features x rows): the weights are the MFMA A operand, so a lane's four
 // accumulator registers are four CONSECUTIVE output features (n0 + 16*wt + 4*(lane>>4) + e) of ONE activation

@@ -207,14 +207,7 @@ __device__ __forceinline__ void pj_glds16(const void* sbase, unsigned voff, unsi
     // the M0 wait state).  Rounds 3 - 4 had `s_nop 0` here: a spec violation, though no failure could be tied to it.
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sb), "s"(lds_addr) : "memory", "m0");
 }
-// hi | lo split with the hi plane DEFINED by the packed registers the MFMA reads.  hipcc may select f16(x) twice -- inside the packed
-// conversion that builds the operand vector (v_cvt_pk_f16_f32 of the fp32 value) and again for the scalar that feeds lo, and when x
-// is a product or a sum it folds that second one into v_fma_mixlo_f16, which rounds ONCE from the exact result.  At an fp32 value
-// that lies exactly between two f16 numbers the two selections differ by one f16 ulp and hi + lo is off by that ulp: with
-// -fno-slp-vectorize the fused form did exactly that to a probability of 0.0625 - 2^-16 (one query row of 8192, 1e-4 against the
-// oracle; the packed build had happened to extract lo's operand from the packed registers).  The empty asm makes the vector opaque:
-// what lo is computed from is what the MFMA multiplies.  No instruction.
-template <class V> __device__ __forceinline__ void pf_pin(V& v) { asm("" : "+v"(v)); }
+// (pf_pin -- lo is computed from the hi the MFMA reads -- lives in common.h: the producers of the shared k fragments use it too)
 template <int N> __device__ __forceinline__ void pj_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory"); }
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n (the immediate has to be a constant): at most n vector memory operations of this
 // wave are outstanding (LOADS complete in order among themselves; a store may complete before an older load, see proj_head)
@@ -247,8 +240,17 @@ __host__ __device__ __forceinline__ constexpr int pj_vp_floats(int LP) {        
 struct PjW { half8 h[4], l[4]; };
 // KF (pf_ipa_attn_args.k_from_s, ABI 58): THE KEYS ARE THE NODE STATE.  q_h . k_h = s_i^T (W_q,h^T W_k,h) s_j + terms that are constant along
 // a softmax row, so with the query rows packed as W_k,h^T (W_q,h s + b_q,h) (engine.fold_keys_into_queries: weights only) the k
-// operand of the first product is the row of s itself -- every wave writes its 16 rows as operand fragments before the tile loop and
-// the eight k tiles leave the weight stream altogether: 23 tiles in 8 chunks instead of 31 in 11 (a first build only passed over their
+// operand of the first product is the row of s itself and the eight k tiles leave the weight stream altogether: 23 tiles in 8 chunks
+// instead of 31 in 11.  Where the fragments come from:
+//   KS (hi | lo f16 fragments)   ONE buffer per SAMPLE (pf_ipa_attn_args.k_frag_s, layout at pf_kfrag_put in common.h), written by the
+//        kernel that produced s (input_mixer_kernel / the last node_tfmr_kernel of the block before) or, for a caller without such a
+//        producer, by ipa_kfrag_kernel in front of this launch.  The prologue does NOTHING for the keys: until round 8 each of the
+//        sample's eight head workgroups re-read its rows of s and stored the same 64 KiB into its own slice of att_vt -- two
+//        serialised load -> convert -> store batches in front of the first LDS-DMA issue of a cold workgroup (6.6 k of its 84 k
+//        cycles, profiles/r06/README.md section 4), and eight copies of the fragments competing for the XCD's L2 in the score loop.
+//   fp32 fragments (L <= 64, the form with the pair phase)   every wave writes its 16 rows into the head's slice of att_vt before
+//        the tile loop, as before.
+// (a first build of the fold only passed over the k tiles'
 // MFMAs and fragment reads and let their LDS-DMA pieces flow: no gain at all -- the prologue is bound by its staging pipeline, one
 // chunk per L2 -> LDS round trip, not by what the waves do with a chunk; profiles/r05/README.md).
 template <bool KF> __device__ __forceinline__ constexpr int pj_ntiles() { return KF ? PJ_TILES - 8 : PJ_TILES; }                 // tiles that are staged and computed
@@ -321,9 +323,8 @@ __device__ __forceinline__ void proj_head(const pf_ipa_attn_args& a, size_t rowb
         }
     }
     PROFS(31);
-    if constexpr (KF) {
-        _Float16* kfrag = VTH + (size_t)8 * (VTG >> 5) * 1024 + (size_t)tile * 4096 + lane * 8;  // (layout: below; formed here for this form only --
-                                                                                                 //  the other form keeps its instruction stream)
+    if constexpr (KF && !KS) {                 // (KS: the sample's shared fragments exist already, see above -- nothing to do here)
+        float* kfrag32 = reinterpret_cast<float*>(VTH + (size_t)8 * (VTG >> 5) * 1024 + (size_t)tile * 4096);   // (layout: below)
         // the k fragments of this wave's 16 rows straight from the node state, in the slot order the tiles below would have produced:
         // lane (key r, g) holds channels 16 t + 4 g .. + 3 of "tile" t.  Loads and stores OLDER than every LDS-DMA piece (as the row
         // loads above): an outstanding store only makes a counted wait below wait longer.
@@ -335,23 +336,7 @@ __device__ __forceinline__ void proj_head(const pf_ipa_attn_args& a, size_t rowb
 #pragma unroll
                 for (int u = 0; u < 4; ++u) kt[u] = *reinterpret_cast<const float4*>(krow + 16 * (4 * hb + u));
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int t8 = 4 * hb + u;
-                    const float v[4] = {kt[u].x, kt[u].y, kt[u].z, kt[u].w};
-                    if constexpr (KS) {
-                        half4 hi, lo;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) hi[e] = (_Float16)v[e];
-                        pf_pin(hi);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) lo[e] = (_Float16)(v[e] - (float)hi[e]);
-                        _Float16* d = kfrag + (t8 >> 1) * 1024 + (t8 & 1) * 4;
-                        *reinterpret_cast<half4*>(d) = hi;
-                        *reinterpret_cast<half4*>(d + 512) = lo;
-                    } else {
-                        *reinterpret_cast<float4*>(reinterpret_cast<float*>(kfrag - lane * 8) + t8 * 256 + lane * 4) = kt[u];
-                    }
-                }
+                for (int u = 0; u < 4; ++u) *reinterpret_cast<float4*>(kfrag32 + (4 * hb + u) * 256 + lane * 4) = kt[u];
             }
         }
     }
@@ -684,7 +669,7 @@ __device__ __forceinline__ void proj_head16(const pf_ipa_attn_args& a, size_t ro
 // variant: as a run-time test inside loadk the branch cost the loop its load pipelining (113 -> 166 us at B=64, L=144, and 136 with the
 // fragments: hipcc drains vmcnt at every control-flow join -- the lesson of round 2 once more).
 template <bool VEC4, bool FUSE = false, bool PROJ = false, bool KFRAG = false, bool KF = false, bool HELP = true>   // (HELP: with PROJ, helper waves may exist (L <= 64) -- proj_head's role is a run-time value; false (L > 64): role 0 at compile time, the straight-line prologue;  KF: with PROJ, the keys are the node state: pj_live)  L % 4 == 0: bias / probability rows are read / written as float4; FUSE: pair aggregation on a.dz (fp32) here, P not stored; PROJ: the head's projection here (proj_head)
-__global__ __launch_bounds__(512) void ipa_scores_kernel(pf_ipa_attn_args a, int nrb, int rows_per_block, int LP, int SLD) {
+__global__ __launch_bounds__(512) void ipa_scores_kernel(pf_ipa_attn_args a, int nrb, int rows_per_block, int LP, int SLD, unsigned kfs_b /* bytes per sample of a.k_frag_s */) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr bool KSPLIT = PROJ && !FUSE;         // first product on split f16 MFMAs, k rows as hi | lo fragments (proj_head<true>)
     const int L = a.L;
@@ -728,7 +713,9 @@ __global__ __launch_bounds__(512) void ipa_scores_kernel(pf_ipa_attn_args a, int
     const float* kbase = a.proj + rowb * a.ldp + OFF_KV + h * 2 * C + 4 * g;
     // PROJ: the k rows come from the launch's scratch in fragment order (proj_head): tile t, step s = one contiguous KiB
     const char* kfr_u = nullptr;
-    if constexpr (PROJ) {
+    if constexpr (KSPLIT && KF) {                  // the keys are the node state: the SAMPLE's fragments, shared by its eight heads (proj_head)
+        kfr_u = reinterpret_cast<const char*>(a.k_frag_s) + (size_t)b * kfs_b;
+    } else if constexpr (PROJ) {
         const int VTG = (L + 31) & ~31;
         kfr_u = reinterpret_cast<const char*>(a.att_vt) + (((size_t)b * H + h) * 512 * VTG + (size_t)8 * (VTG >> 5) * 1024) * sizeof(_Float16);
     }
@@ -901,6 +888,9 @@ __global__ __launch_bounds__(512) void ipa_scores_kernel(pf_ipa_attn_args a, int
             float v = acc[e] * scale_qk + bj[e];
             v = v + (-0.5f) * (gamma * (d2[0] + d2[1]));
             v = v + 1e5f * (mi * MJ[j] - 1.f);
+            // (a SELECT, not arithmetic: the rows of the partial tile from Le on hold whatever their producer left there -- with the
+            //  shared k fragments the sample's own masked rows or stale finite data -- and element (key j, query r) of the product
+            //  depends on no other key row, so nothing of them survives this line)
             if constexpr (TAIL) v = j < Le ? v : -3.0e38f;
             sv[e] = v;
             mx = fmaxf(mx, v);
@@ -1752,6 +1742,22 @@ __global__ __launch_bounds__(256) void ipa_pair_dz16_kernel(pf_ipa_attn_args a) 
     *reinterpret_cast<float2*>(a.feats + (size_t)row * PF_IPA_FEATS + 1408 + h * 16 + c) = make_float2(z2[0] + bd.x, z2[1] + bd.y);
 }
 
+// The shared k fragments of the keys-are-the-state form for a caller WITHOUT a producer in front (pf_ipa_attn_args.k_frag_s == NULL:
+// the stand-alone calls of pf_ipa_attn_fwd): rows of s_in -> fragments (pf_kfrag_put: the producers' conversion and layout), into
+// head 0's k slice of the sample's att_vt scratch, which no score workgroup writes in this form.  Workgroup = (sample, 16-key tile),
+// wave = 16-channel tile t8, lane (key r, g).  Rows of a partial last tile from the key end on repeat row Le - 1, as the prologue
+// wrote them until round 8; tiles beyond the key end are never read and not written.
+__global__ __launch_bounds__(512) void ipa_kfrag_kernel(pf_ipa_attn_args a, _Float16* kf, unsigned kfs_b) {
+    const int tiles = (a.L + 15) >> 4;
+    const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
+    const int Le = a.key_end ? min(__builtin_amdgcn_readfirstlane(a.key_end[b]), a.L) : a.L;
+    if (16 * tile >= Le) return;
+    const int t8 = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+    const float4 x = *reinterpret_cast<const float4*>(a.s_in + ((size_t)b * a.L + min(16 * tile + r, Le - 1)) * 128 + 16 * t8 + 4 * g);
+    const float v[4] = {x.x, x.y, x.z, x.w};
+    pf_kfrag_put(reinterpret_cast<_Float16*>(reinterpret_cast<char*>(kf) + (size_t)b * kfs_b), 16 * tile + r, t8, g, v);
+}
+
 }  // namespace
 
 // two-kernel IPA (called by pf_ipa_attn_fwd, ipa_attn.hip): requires a->bias and a->p_out, L <= 256
@@ -1812,6 +1818,7 @@ int pf_ipa_split_launch(const pf_ipa_attn_args* a, hipStream_t s) {
         const int nrb = (tiles + wmax - 1) / wmax;
         const int wpb = (tiles + nrb - 1) / nrb;
         const size_t lds = fixed + wpb * per_wave;
+        unsigned kfs_b = 0;                                      // bytes per sample of the shared k fragments (the keys-are-the-state form below)
         static PfOncePerDevice attr_set;
         if (attr_set.first()) {
             (void)hipFuncSetAttribute((const void*)ipa_scores_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1860,9 +1867,25 @@ int pf_ipa_split_launch(const pf_ipa_attn_args* a, hipStream_t s) {
             if (ldsp > 160 * 1024) return PF_E_TOOLARGE;
             // L <= 64: as many helper waves as query waves for the prologue (proj_head roles)
             const int nwv = wpb <= 4 ? 2 * wpb : wpb;
+            // keys = node state as hi | lo fragments (k_from_s without the pair phase): ONE fragment buffer per sample, [B][tiles][8 KiB],
+            // normally written by the producer of s_in (pf_input_mixer_args / pf_node_tfmr_args.k_frag_s).  A caller without one gets
+            // them from a small kernel in front, in head 0's k slice of each sample's att_vt scratch (unused by the score kernel in
+            // this form): the same bytes, so the score kernel exists in ONE form either way.
+            pf_ipa_attn_args ak = *a;
+            if (a->k_from_s && !fuse) {
+                kfs_b = (unsigned)tiles * PF_KFRAG_TILE_B;
+                if (!a->k_frag_s) {
+                    const int VTG = (L + 31) & ~31;
+                    kfs_b = (unsigned)((size_t)H * 512 * VTG * sizeof(_Float16));
+                    _Float16* kf = reinterpret_cast<_Float16*>(const_cast<void*>(a->att_vt)) + (size_t)8 * (VTG >> 5) * 1024;
+                    ak.k_frag_s = kf;
+                    hipLaunchKernelGGL(ipa_kfrag_kernel, dim3((unsigned)(a->B * tiles)), dim3(512), 0, s, ak, kf, kfs_b);
+                    PF_CHECK_LAUNCH();
+                }
+            }
 #define PF_SCORES_PJ(FUSEv, KFv) do { \
-                if (nwv != wpb) hipLaunchKernelGGL((ipa_scores_kernel<true, FUSEv, true, false, KFv, true>), dim3((unsigned)(a->B * H * nrb)), dim3(64 * nwv), ldsp, s, *a, nrb, 16 * wpb, LP, SLD); \
-                else hipLaunchKernelGGL((ipa_scores_kernel<true, FUSEv, true, false, KFv, false>), dim3((unsigned)(a->B * H * nrb)), dim3(64 * nwv), ldsp, s, *a, nrb, 16 * wpb, LP, SLD); } while (0)
+                if (nwv != wpb) hipLaunchKernelGGL((ipa_scores_kernel<true, FUSEv, true, false, KFv, true>), dim3((unsigned)(a->B * H * nrb)), dim3(64 * nwv), ldsp, s, ak, nrb, 16 * wpb, LP, SLD, kfs_b); \
+                else hipLaunchKernelGGL((ipa_scores_kernel<true, FUSEv, true, false, KFv, false>), dim3((unsigned)(a->B * H * nrb)), dim3(64 * nwv), ldsp, s, ak, nrb, 16 * wpb, LP, SLD, kfs_b); } while (0)
             if (a->k_from_s) {
                 if (fuse) PF_SCORES_PJ(true, true);
                 else PF_SCORES_PJ(false, true);
@@ -1890,15 +1913,15 @@ int pf_ipa_split_launch(const pf_ipa_attn_args* a, hipStream_t s) {
             if (fuse) hipLaunchKernelGGL((ipa_scores16_kernel<true>), g16, b16, lds16, s, *a, nrb16, 16 * wpb16, SLD16);
             else hipLaunchKernelGGL(ipa_scores16_kernel<false>, g16, b16, lds16, s, *a, nrb16, 16 * wpb16, SLD16);
         } else if (a->k_frag) {                     // (L % 16 == 0 checked above)
-            if (fuse) hipLaunchKernelGGL((ipa_scores_kernel<true, true, false, true>), dim3((unsigned)(a->B * H * nrb)), dim3(64 * wpb), lds, s, *a, nrb, 16 * wpb, LP, SLD);
-            else hipLaunchKernelGGL((ipa_scores_kernel<true, false, false, true>), dim3((unsigned)(a->B * H * nrb)), dim3(64 * wpb), lds, s, *a, nrb, 16 * wpb, LP, SLD);
+            if (fuse) hipLaunchKernelGGL((ipa_scores_kernel<true, true, false, true>), dim3((unsigned)(a->B * H * nrb)), dim3(64 * wpb), lds, s, *a, nrb, 16 * wpb, LP, SLD, kfs_b);
+            else hipLaunchKernelGGL((ipa_scores_kernel<true, false, false, true>), dim3((unsigned)(a->B * H * nrb)), dim3(64 * wpb), lds, s, *a, nrb, 16 * wpb, LP, SLD, kfs_b);
         } else if (fuse) {
-            if ((L & 3) == 0) hipLaunchKernelGGL((ipa_scores_kernel<true, true>), dim3((unsigned)(a->B * H * nrb)), dim3(64 * wpb), lds, s, *a, nrb, 16 * wpb, LP, SLD);
-            else hipLaunchKernelGGL((ipa_scores_kernel<false, true>), dim3((unsigned)(a->B * H * nrb)), dim3(64 * wpb), lds, s, *a, nrb, 16 * wpb, LP, SLD);
+            if ((L & 3) == 0) hipLaunchKernelGGL((ipa_scores_kernel<true, true>), dim3((unsigned)(a->B * H * nrb)), dim3(64 * wpb), lds, s, *a, nrb, 16 * wpb, LP, SLD, kfs_b);
+            else hipLaunchKernelGGL((ipa_scores_kernel<false, true>), dim3((unsigned)(a->B * H * nrb)), dim3(64 * wpb), lds, s, *a, nrb, 16 * wpb, LP, SLD, kfs_b);
         } else if ((L & 3) == 0)
-            hipLaunchKernelGGL(ipa_scores_kernel<true>, dim3((unsigned)(a->B * H * nrb)), dim3(64 * wpb), lds, s, *a, nrb, 16 * wpb, LP, SLD);
+            hipLaunchKernelGGL(ipa_scores_kernel<true>, dim3((unsigned)(a->B * H * nrb)), dim3(64 * wpb), lds, s, *a, nrb, 16 * wpb, LP, SLD, kfs_b);
         else
-            hipLaunchKernelGGL(ipa_scores_kernel<false>, dim3((unsigned)(a->B * H * nrb)), dim3(64 * wpb), lds, s, *a, nrb, 16 * wpb, LP, SLD);
+            hipLaunchKernelGGL(ipa_scores_kernel<false>, dim3((unsigned)(a->B * H * nrb)), dim3(64 * wpb), lds, s, *a, nrb, 16 * wpb, LP, SLD, kfs_b);
         PF_CHECK_LAUNCH();
     }
     if (rc) return rc;

@@ -57,8 +57,11 @@ __device__ __forceinline__ void ln_load(LnParams& p, const float* __restrict__ g
     p.g[0] = g0.x; p.g[1] = g0.y; p.g[2] = g0.z; p.g[3] = g0.w; p.g[4] = g1.x; p.g[5] = g1.y; p.g[6] = g1.z; p.g[7] = g1.w;
     p.b[0] = b0.x; p.b[1] = b0.y; p.b[2] = b0.z; p.b[3] = b0.w; p.b[4] = b1.x; p.b[5] = b1.y; p.b[6] = b1.z; p.b[7] = b1.w;
 }
-template <int ROWS = 16>
-__device__ __forceinline__ void ln_tile(float* T, const LnParams& p, float mk, Planes out, int m0, int M, float* gout) {
+// KFR (the block's last LayerNorm, inference): rows below M also go to the sample's shared k fragments of the next attention
+// (pf_kfrag_put; kf = the sample's buffer or NULL, i0 = row of tile row 0 within its sample) -- the lane's columns 8 sub .. + 3 and
+// 8 sub + 4 .. + 7 are the four channels of 16-channel tile sub / 2 that lanes g = 2 (sub & 1) and g + 1 of the score kernel read.
+template <int ROWS = 16, bool KFR = false>
+__device__ __forceinline__ void ln_tile(float* T, const LnParams& p, float mk, Planes out, int m0, int M, float* gout, _Float16* kf = nullptr, int i0 = 0) {
     const int tid = threadIdx.x;
     if (tid < 16 * ROWS) {
         const int row = tid >> 4, sub = tid & 15, m = m0 + row;
@@ -92,6 +95,12 @@ __device__ __forceinline__ void ln_tile(float* T, const LnParams& p, float mk, P
         if (gout && m < M) {
             *reinterpret_cast<float4*>(gout + (size_t)m * 128 + 8 * sub) = make_float4(y[0], y[1], y[2], y[3]);
             *reinterpret_cast<float4*>(gout + (size_t)m * 128 + 8 * sub + 4) = make_float4(y[4], y[5], y[6], y[7]);
+        }
+        if constexpr (KFR) {
+            if (kf && m < M) {
+                pf_kfrag_put(kf, i0 + row, sub >> 1, 2 * (sub & 1), y0);
+                pf_kfrag_put(kf, i0 + row, sub >> 1, 2 * (sub & 1) + 1, y1);
+            }
         }
     }
 }
@@ -798,7 +807,9 @@ __global__ __launch_bounds__(NTHR, PF_NT_MINW) void node_tfmr_kernel(pf_node_tfm
             dump4(a.dump[9], rt, v[0] + s0.x, v[1] + s0.y, v[2] + s0.z, v[3] + s0.w);                            // h3 = linear_3(t2) + s2
         }
         __syncthreads();
-        ln_tile<TR>(T0, ln3, lnmask_ld * (lnrow < M ? 1.f : 0.f), Xb, m0, M, a.s_out);           // s_new (masked) -> global + planes Xb
+        // s_new (masked) -> global + planes Xb (+ the next attention's k fragments, pf_node_tfmr_args.k_frag_s)
+        _Float16* kfs = DUMP || !a.k_frag_s ? nullptr : reinterpret_cast<_Float16*>(a.k_frag_s) + (size_t)b * ((L + 15) >> 4) * (PF_KFRAG_TILE_B / 2);
+        ln_tile<TR, !DUMP>(T0, ln3, lnmask_ld * (lnrow < M ? 1.f : 0.f), Xb, m0, M, a.s_out, kfs, i0);
         __syncthreads();
         PROF(9);
         if (do_bb || do_init) {
@@ -1005,6 +1016,11 @@ __global__ __launch_bounds__(NTHR) void input_mixer_kernel(pf_input_mixer_args a
         y.x = (join(am[0], ac[0], 0) + b2.x) * rmask; y.y = (join(am[0], ac[0], 1) + b2.y) * rmask;
         y.z = (join(am[0], ac[0], 2) + b2.z) * rmask; y.w = (join(am[0], ac[0], 3) + b2.w) * rmask;
         *reinterpret_cast<float4*>(a.s_out + (size_t)mr * 128 + n) = y;
+        if (a.k_frag_s) {                                 // block 0's shared k fragments: this lane's four channels are those of lane
+            const int b = mr / a.L;                       //  (key, g) of 16-channel tile `wave` in the score kernel's order (pf_kfrag_put)
+            const float v[4] = {y.x, y.y, y.z, y.w};
+            pf_kfrag_put(reinterpret_cast<_Float16*>(a.k_frag_s) + (size_t)b * ((a.L + 15) >> 4) * (PF_KFRAG_TILE_B / 2), mr - b * a.L, wave, g, v);
+        }
     }
 }
 

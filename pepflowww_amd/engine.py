@@ -716,6 +716,14 @@ class DenoiseEngine:
         self.att_vt32 = None
         if self.fused_proj and not self.att_planes:
             self.att_vt32 = torch.zeros(B * 8 * 512 * ((L + 31) // 32 * 32), dtype=torch.float16, device=device)
+        # keys = the node state without the fused pair phase (64 < L <= 128 by default): the k operand fragments exist ONCE per sample
+        # (pf_ipa_attn_args.k_frag_s, [B][ceil(L / 16) tiles][8 KiB]) and are written by whoever writes s -- the input mixer for block 0,
+        # each block's last node_tfmr launch for the next -- instead of eight times per sample by the score kernel's prologue.  Zeroed:
+        # rows nobody writes (beyond L; tiles the node kernels skip in a padded batch) must be finite.  The k half of att_vt32 is then
+        # only the scratch of a stand-alone pf_ipa_attn_fwd call; it keeps its size (the value planes are addressed per (sample, head)).
+        self.k_frag_s = None
+        if self.att_vt32 is not None and self.k_fold and not self.fused_pair:
+            self.k_frag_s = torch.zeros(B * ((L + 15) // 16) * 4096, dtype=torch.float16, device=device)
         # fp32 mode with the projection LAUNCH (L > 128 or L % 4 != 0 ...) and the two-kernel attention: the k columns of the projection go
         # to a scratch in the fragment order of the score kernel's first product instead of `proj` (pf_linear_args.k_frag /
         # pf_ipa_attn_args.k_frag: one contiguous KiB per load instead of sixteen rows x 64 bytes).  options={'k_frag': ...} forces it (A/B runs).
@@ -899,6 +907,8 @@ class DenoiseEngine:
         ma.w0_f16, ma.b0, ma.w2_f16, ma.b2 = w["mix0.w16"].data_ptr(), w["mix0.b"].data_ptr(), w["mix2.w16"].data_ptr(), w["mix2.b"].data_ptr()
         ma.mask, ma.rot, ma.quat, ma.s_out, ma.B, ma.L = self.mask.data_ptr(), self.rot_t.data_ptr(), self.quat.data_ptr(), self.s.data_ptr(), B, L
         ma.single_pass = int(self.precision == "f16")
+        kfs = self.k_frag_s.data_ptr() if self.k_frag_s is not None else None    # shared k fragments: producers and consumer below
+        ma.k_frag_s = kfs
         self._keep.append(ma)
         plan.append((lib.pf_input_mixer_fwd, C.byref(ma), "pf_input_mixer_fwd"))
 
@@ -952,6 +962,7 @@ class DenoiseEngine:
                 pk = ("projpm" if self.o_premul else "projp") + ("k" if self.k_fold else "")
                 ia.s_in, ia.proj_w_f16, ia.proj_bias = self.s.data_ptr(), w[f"{b}.{pk}.w16"].data_ptr(), w[f"{b}.{pk}.b"].data_ptr()
                 ia.k_from_s = int(self.k_fold)
+                ia.k_frag_s = kfs
                 if self.att_vt32 is not None:
                     ia.att_vt = self.att_vt32.data_ptr()
             self._keep.append(ia)
@@ -1000,6 +1011,7 @@ class DenoiseEngine:
                     ta.quat_in, ta.rot_in, ta.trans_in = self.quat.data_ptr(), rot.data_ptr(), trans.data_ptr()
                     ta.quat_out, ta.rot_out, ta.trans_out = self.quat.data_ptr(), self.rot.data_ptr(), self.trans.data_ptr()
                     ta.has_et = int(b < N_BLOCKS - 1)
+                    ta.k_frag_s = kfs if ta.has_et else None       # (the last block's s feeds no attention)
                     if not ta.has_et and self.row_on is not None:
                         ta.row_on = self.row_on.data_ptr()
                     if not ta.has_et:

@@ -99,7 +99,11 @@ def main():
                                "splits through pf_pin, query points handed over in registers.  HELP = true instantiations (L <= 64, run-time roles) and the f16 "
                                "kernels: the machine code of round 5 (0 of 20 000 launches in each of three kernel forms, profiles/r05/r05_campaign_noslp.txt).  "
                                "HELP = false instantiations (round 6: straight-line prologue beyond L = 64): fresh-process campaign "
-                               "profiles/r06/r06_campaign_straight.txt (0 of 96 processes, six shapes x two modes), tests/test_gpu_fresh_process.py, the GPU suite",
+                               "profiles/r06/r06_campaign_straight.txt (0 of 96 processes, six shapes x two modes), tests/test_gpu_fresh_process.py, the GPU suite.  "
+                               "Round 8 (the k fragments of the keys-are-the-state form shared per sample: the KF instantiations without the pair phase lose "
+                               "their k loads and stores in front of the first LDS-DMA issue, every instantiation gains one kernel argument): the GPU suite "
+                               "with tests/test_gpu_fresh_process.py, the repeat-launch bitwise tests and tests/test_gpu_shared_keys.py at the final sources, "
+                               "outputs of cfg2 / cfg3 / cfg4 / f16@cfg4 byte-equal to the parent library (profiles/r08/README.md)",
                "kernels": got}
         with open(PIN, "w") as f:
             json.dump(pin, f, indent=1, sort_keys=True)
