@@ -13,7 +13,9 @@
 //        With pf_ipa_attn_args.s_in (64 <= L <= 128) the head's q / k / v / point PROJECTION runs in this kernel's prologue (proj_head);
 //        the two products then read their operands from the launch's scratch (att_vt) in FRAGMENT order -- the k rows as fp32 blocks,
 //        the transposed values as hi | lo f16 blocks: every operand load is one contiguous KiB -- and P.[V | V_pts] runs on split f16
-//        MFMAs (three v_mfma_f32_16x16x32_f16 per product).
+//        MFMAs (three v_mfma_f32_16x16x32_f16 per product).  Without the pair phase that form keeps the scores in registers all the
+//        way (no score rows in LDS: its LDS need is the key / value point tables + the prologue's staging buffers); the forms with
+//        the pair phase, the forms without the projection and ipa_scores16_kernel park them in wave-private LDS rows between the phases.
 //   ipa_pair_kernel    one wave per query row: zbar[h][c] = sum_j P[h][j] z[i][j][c] streamed at HBM rate (z is read exactly once
 //        per block, 256 B/pair = the algorithmic traffic of the step), then o_pair = W_dz zbar + b_dz (linear in z, so the
 //        [B,L,L,16] pair_z tensor of the reference never exists).
@@ -181,6 +183,15 @@ template <int I, int N, class F> __device__ __forceinline__ void cfor_p(F&& f) {
     if constexpr (I < N) {
         f(std::integral_constant<int, I>{});
         cfor_p<I + 1, N>(f);
+    }
+}
+// f(0); if (n > 1) { f(1); if (n > 2) { ... f(N - 1) } }   for a wave-uniform 1 <= n (see the register form of ipa_scores_kernel)
+template <int I, int N, class F> __device__ __forceinline__ void nest_p(int n, F&& f) {
+    if constexpr (I < N) {
+        if (I == 0 || n > I) {
+            f(std::integral_constant<int, I>{});
+            nest_p<I + 1, N>(n, f);
+        }
     }
 }
 constexpr int PJ_TILES = 31;                  // 8 q + 8 k + 8 v + 2 q-point + 5 kv-point tiles of 16 features per head
@@ -657,9 +668,15 @@ __device__ __forceinline__ void proj_head16(const pf_ipa_attn_args& a, size_t ro
     }
 }
 
-// The wave's score tile S[16 queries][L keys] lives in a wave-private LDS region that every lane only ever reads back where it
-// wrote (lane (r, g): row r, keys 16 t + 4 g .. + 3), i.e. it is register spill space under our control: with the tiles held
-// in registers and the tile loops unrolled, hipcc hoisted every tile's loads and spilled 0.9 - 6.8 KB per lane.
+// The wave's score tile S[16 queries][L keys]:
+//   projection inside, no pair phase (KSPLIT: 64 < L <= 128 in the engine's plans, and the L <= 64 calls without the pair phase)
+//        REGISTERS: a lane's four scores of key tile t are the quad sc[t], from the first product through the softmax to the second
+//        product's A operand; the wave's only LDS region is the [16][36] o_pt image of the tail (round 9, at the second product below).
+//   every other form
+//        a wave-private LDS region [16][SLD] that a lane only ever reads back where it wrote (lane (r, g): row r, keys 16 t + 4 g
+//        .. + 3) -- except in the pair phase (FUSE), which reads other lanes' columns and is why these forms keep the rows.  A first
+//        register build (round 2: tile loops unrolled, nothing else) had hipcc hoist every tile's loads and spill 0.9 - 6.8 KB
+//        per lane; the register form fences every tile with a scheduling barrier.
 // The tile loops contain NO branch: every load is unconditional (clamped index), query rows beyond L are exact duplicates of row
 // L - 1 (same operands, same results, stored to the same place), and a partial last key tile is handled by ONE guarded pass after
 // the loop.  (First version: conditional prefetches and guarded stores inside the loops -- hipcc emits s_waitcnt vmcnt(0) at
@@ -837,7 +854,7 @@ __global__ __launch_bounds__(512) void ipa_scores_kernel(pf_ipa_attn_args a, int
     float mx = -3.0e38f;
     // one key tile: bias + scale * K Q^T - gamma/2 * point distances + mask -> LDS.  TAIL: the partial last tile (keys beyond L
     // read clamped addresses and get -inf)
-    auto qk_tile = [&](int t, const float4 (&kf)[8], auto tail) {
+    auto qk_tile = [&](int t, const float4 (&kf)[8], auto tail, float4& out) __attribute__((always_inline)) {
         constexpr bool TAIL = decltype(tail)::value;
         const int jb = 16 * t + 4 * g;
         float bj[4];
@@ -895,23 +912,31 @@ __global__ __launch_bounds__(512) void ipa_scores_kernel(pf_ipa_attn_args a, int
             sv[e] = v;
             mx = fmaxf(mx, v);
         }
-        *reinterpret_cast<float4*>(srow + 16 * t) = make_float4(sv[0], sv[1], sv[2], sv[3]);
+        out = make_float4(sv[0], sv[1], sv[2], sv[3]);
+    };
+    auto qk_tile_lds = [&](int t, const float4 (&kf)[8], auto tail) {
+        float4 s4;
+        qk_tile(t, kf, tail, s4);
+        *reinterpret_cast<float4*>(srow + 16 * t) = s4;
     };
     // two tiles per trip, the two fragment buffers alternating: with a copy "current = next" at the end of a one-tile trip hipcc
     // hoists the copies into the MFMA sequence and waits for the prefetch ~600 cycles after issuing it
     int t = 0;
+    float inv;
+    // (KSPLIT: scores, softmax and the second product are one register-resident body, at the second product below)
+    if constexpr (!KSPLIT) {
     for (; t + 1 < ktf; t += 2) {
         loadk(t + 1, kn);
-        qk_tile(t, kf, std::false_type{});
+        qk_tile_lds(t, kf, std::false_type{});
         loadk(min(t + 2, kt - 1), kf);                           // unconditional (the last trip re-reads a valid tile)
-        qk_tile(t + 1, kn, std::false_type{});
+        qk_tile_lds(t + 1, kn, std::false_type{});
     }
     if (ktf & 1) {                                               // (wave-uniform, outside the loop)
         loadk(kt - 1, kn);
-        qk_tile(ktf - 1, kf, std::false_type{});
-        if (kt > ktf) qk_tile(ktf, kn, std::true_type{});
+        qk_tile_lds(ktf - 1, kf, std::false_type{});
+        if (kt > ktf) qk_tile_lds(ktf, kn, std::true_type{});
     } else if (kt > ktf) {
-        qk_tile(ktf, kf, std::true_type{});
+        qk_tile_lds(ktf, kf, std::true_type{});
     }
     PROFS(2);
     // ---- softmax over the keys of query r (spread over the 4 lanes r, r+16, r+32, r+48) ----
@@ -924,14 +949,15 @@ __global__ __launch_bounds__(512) void ipa_scores_kernel(pf_ipa_attn_args a, int
         *reinterpret_cast<float4*>(srow + 16 * t) = v;
     }
     sum = sum_xor32(sum_xor16(sum));
-    const float inv = 1.f / sum;
-    PROFS(3);
+    inv = 1.f / sum;
+    }
+    if constexpr (!KSPLIT) PROFS(3);                             // (KSPLIT: stamps 2, 3 and 7 sit in its body below)
     if constexpr (FUSE) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the phase reads other lanes' columns of the wave's region
         __builtin_amdgcn_wave_barrier();
         pair_dz_phase<false>(a, rowb, h, i0, Le, kt, SW + (size_t)wave * 16 * SLD, SLD, inv, lane);
     }
-    PROFS(7);
+    if constexpr (!KSPLIT) PROFS(7);
     float* prow = FUSE ? nullptr : a.p_out + (((size_t)b * H + h) * L + iq) * L;
 
     // ---- [o | o_pt] = P [V | V_pts]: A = P (this lane: query r, key 16 t + 4 g + tt in MFMA tt), B = value rows.
@@ -941,8 +967,10 @@ __global__ __launch_bounds__(512) void ipa_scores_kernel(pf_ipa_attn_args a, int
     //      The normalised probabilities are written out ([B,8,L,L]) on the way ----
     constexpr int NTC = 11;
     f32x4 O[NTC];
+    if constexpr (!KSPLIT) {                                     // (KSPLIT: cleared in its body, behind the score tiles -- 44 registers)
 #pragma unroll
-    for (int n = 0; n < NTC; ++n) O[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < NTC; ++n) O[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
     if constexpr (PROJ) {
         // ---- PROJ form: the second product on v_mfma_f32_16x16x32_f16, three MFMAs per product (P hi x V hi + P hi x V lo + P lo x V hi
         //      into ONE accumulator: lo halves unscaled, gfx950's f16 MFMA honours subnormal operands) -- 33 MFMAs of 16 cycles per 32
@@ -956,37 +984,35 @@ __global__ __launch_bounds__(512) void ipa_scores_kernel(pf_ipa_attn_args a, int
         const unsigned vt_lane = (unsigned)lane * 16u;
         const _Float16* vpt = reinterpret_cast<const _Float16*>(VP) + r * VTL + 8 * g;
         const int steps = (kt + 1) >> 1;
+        const size_t tstride = (size_t)(VTG >> 5) * 2048;
+        auto loadvp = [&](int st, int plane, half8 (&v)[8]) __attribute__((always_inline)) {   // block (tile n, step st): hi KiB | lo KiB
+            const char* su = vt_u + (size_t)st * 2048 + plane * 1024;
+            unsigned vo = vt_lane;                   // (opaque per call: otherwise hipcc forms one 64-bit lane address per tile and keeps
+            asm volatile("" : "+v"(vo));             //  them in VGPRs across the steps -- with this the loads are scalar base + lane offset)
+#pragma unroll
+            for (int n = 0; n < 8; ++n) v[n] = *reinterpret_cast<const half8*>(su + n * tstride + vo);
+        };
         auto loadv16 = [&](int st, half8 (&vh)[8], half8 (&vl)[8]) {
-            const char* su = vt_u + (size_t)st * 2048;                         // block (tile n, step st): hi KiB | lo KiB
-            const size_t tstride = (size_t)(VTG >> 5) * 2048;
+            const char* su = vt_u + (size_t)st * 2048;
 #pragma unroll
             for (int n = 0; n < 8; ++n) {
                 vh[n] = *reinterpret_cast<const half8*>(su + n * tstride + vt_lane);
                 vl[n] = *reinterpret_cast<const half8*>(su + n * tstride + vt_lane + 1024);
             }
         };
-        auto pv_step = [&](int st, const half8 (&vh)[8], const half8 (&vl)[8]) {
-            const int t0 = 2 * st, t1 = 2 * st + 1;
-            float4 p0 = *reinterpret_cast<const float4*>(srow + 16 * t0);
-            float4 p1 = *reinterpret_cast<const float4*>(srow + 16 * min(t1, kt - 1));
-            p0.x *= inv; p0.y *= inv; p0.z *= inv; p0.w *= inv;
-            p1.x *= inv; p1.y *= inv; p1.z *= inv; p1.w *= inv;
-            if (t1 >= kt) p1 = make_float4(0.f, 0.f, 0.f, 0.f);          // (wave-uniform: an odd number of key tiles)
-            if constexpr (!FUSE) {                                        // the normalised probabilities, as the fp32 form writes them
-                auto put = [&](int t, const float4& p) {
-                    const int jb = 16 * t + 4 * g;
-                    if (16 * t + 16 <= Le) {
-                        *reinterpret_cast<float4*>(prow + jb) = p;        // (L % 4 == 0 in this form; duplicate rows store identical values)
-                    } else {
-                        if (jb < Le) prow[jb] = p.x;
-                        if (jb + 1 < Le) prow[jb + 1] = p.y;
-                        if (jb + 2 < Le) prow[jb + 2] = p.z;
-                        if (jb + 3 < Le) prow[jb + 3] = p.w;
-                    }
-                };
-                put(t0, p0);
-                if (t1 < kt) put(t1, p1);
-            }
+        // the normalised probabilities of tile t, as the fp32 form writes them: a tile below the key end (L % 4 == 0 in this form;
+        // duplicate rows store identical values), and the partial last tile
+        auto put = [&](int t, const float4& p) __attribute__((always_inline)) { *reinterpret_cast<float4*>(prow + 16 * t + 4 * g) = p; };
+        auto put_tail = [&](int t, const float4& p) __attribute__((always_inline)) {
+            const int jb = 16 * t + 4 * g;
+            if (jb < Le) prow[jb] = p.x;
+            if (jb + 1 < Le) prow[jb + 1] = p.y;
+            if (jb + 2 < Le) prow[jb + 2] = p.z;
+            if (jb + 3 < Le) prow[jb + 3] = p.w;
+        };
+        // one 32-key step on the normalised probabilities p0 | p1 of tiles 2 st | 2 st + 1 (zeros for a tile beyond the last)
+        // (lo_done: called once the lo plane's MFMAs are issued -- the registers of vl are free from there on)
+        auto pv_mma = [&](int st, const float4& p0, const float4& p1, const half8 (&vh)[8], const half8 (&vl)[8], auto lo_done) __attribute__((always_inline)) {
             const float pv[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
             half8 ph, pl;
 #pragma unroll
@@ -1009,6 +1035,7 @@ __global__ __launch_bounds__(512) void ipa_scores_kernel(pf_ipa_attn_args a, int
             for (int n = 0; n < 8; ++n) O[n] = mfma_h(ph, vl[n], O[n]);
 #pragma unroll
             for (int n = 0; n < 3; ++n) O[8 + n] = mfma_h(ph, ql[n], O[8 + n]);
+            lo_done();
 #pragma unroll
             for (int n = 0; n < 8; ++n) O[n] = mfma_h(pl, vh[n], O[n]);
 #pragma unroll
@@ -1019,19 +1046,83 @@ __global__ __launch_bounds__(512) void ipa_scores_kernel(pf_ipa_attn_args a, int
             half8 va[8], vc[8];
             for (int st = 0; st < steps; ++st) {
                 loadv16(st, va, vc);
-                pv_step(st, va, vc);
+                const int t1 = 2 * st + 1;                                // this lane's own two float4 of the wave's LDS rows
+                float4 p0 = *reinterpret_cast<const float4*>(srow + 32 * st);
+                float4 p1 = *reinterpret_cast<const float4*>(srow + 16 * min(t1, kt - 1));
+                p0.x *= inv; p0.y *= inv; p0.z *= inv; p0.w *= inv;
+                p1.x *= inv; p1.y *= inv; p1.z *= inv; p1.w *= inv;
+                if (t1 >= kt) p1 = make_float4(0.f, 0.f, 0.f, 0.f);      // (wave-uniform: an odd number of key tiles)
+                pv_mma(st, p0, p1, va, vc, [] {});
             }
         } else {
-            half8 va[8], vc[8], wa[8], wc[8];
-            loadv16(0, va, vc);
-            int st = 0;
-            for (; st + 1 < steps; st += 2) {
-                loadv16(st + 1, wa, wc);
-                pv_step(st, va, vc);
-                loadv16(min(st + 2, steps - 1), va, vc);                  // unconditional (the last trip re-reads a valid step)
-                pv_step(st + 1, wa, wc);
+            // KSPLIT (no pair phase, so no lane ever reads another lane's scores): the lane's four scores of key tile t stay in the
+            // register quad sc[t] from the first product to the second one's A operand; every index is a constant, nothing in scratch.
+            // The tile count kt is workgroup-uniform; tiles and 32-key steps are NESTED guards (tile 0; if (kt > 1) { tile 1; if ... }):
+            // every join lies behind the last tile, so a load requested in front of a guard stays in flight inside it.  (One body per
+            // tile count behind a switch, as ipa_pair_dz_kernel has it through its template parameter, does not work inside one
+            // kernel: hipcc linearises the switch, carries every body's live-in registers through all the others and spills.)
+            // A scheduling barrier in front of every tile / step keeps hipcc from hoisting all the loads to the top (the note above
+            // the kernel).  Same operations in the same order as the LDS form: byte-identical outputs.
+            //   tiles beyond kt: their scores are preset to the mask value, so their probabilities are exact zeros -- the softmax and
+            //   the second product need no guard for them (sum + 0, 0 x a finite value operand: the same bits).
+            //   value operands: THREE sets instead of the LDS form's four (32 score + 44 accumulator + 128 operand registers + the
+            //   point fragments do not fit 256).  The hi planes of the next step are requested at the top of a step into the other of
+            //   two sets; the lo plane has ONE set, dead after the step's second MFMA pass (hi x hi, hi x lo, lo x hi) and requested
+            //   again right there, under the third pass and the next step's first.  Step 0's operands are requested behind the last
+            //   score tile, under the softmax.
+            //   probabilities: normalised in place and stored ([B,8,L,L]) in front of the second product, which then only splits them.
+            constexpr int MAXT = HELP ? 4 : 8;                            // (HELP: L <= 64, at most four tiles)
+            float4 sc[MAXT];
+#pragma unroll
+            for (int tc = 0; tc < MAXT; ++tc) sc[tc] = make_float4(-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f);
+            nest_p<0, MAXT>(kt, [&](auto it) __attribute__((always_inline)) {
+                constexpr int tc = decltype(it)::value;
+                __builtin_amdgcn_sched_barrier(0);
+                // one tile ahead, the two fragment buffers alternating; unconditional (the last tile re-reads itself)
+                if constexpr (tc + 1 < MAXT) loadk(min(tc + 1, kt - 1), (tc & 1) ? kf : kn);
+                const float4 (&kc)[8] = (tc & 1) ? kn : kf;
+                if (Le >= 16 * (tc + 1)) qk_tile(tc, kc, std::false_type{}, sc[tc]);       // (wave-uniform)
+                else qk_tile(tc, kc, std::true_type{}, sc[tc]);
+            });
+            half8 va[8], wa[8], vc[8];
+            __builtin_amdgcn_sched_barrier(0);
+            loadvp(0, 0, va);
+            loadvp(0, 1, vc);
+            __builtin_amdgcn_sched_barrier(0);
+            PROFS(2);
+            mx = max_xor32(max_xor16(mx));
+            float sum = 0.f;
+#pragma unroll
+            for (int tc = 0; tc < MAXT; ++tc) {
+                float4 v = sc[tc];
+                v.x = exp_softmax(v.x - mx); v.y = exp_softmax(v.y - mx); v.z = exp_softmax(v.z - mx); v.w = exp_softmax(v.w - mx);
+                sum += v.x; sum += v.y; sum += v.z; sum += v.w;
+                sc[tc] = v;
             }
-            if (steps & 1) pv_step(steps - 1, va, vc);
+            sum = sum_xor32(sum_xor16(sum));
+            inv = 1.f / sum;
+            PROFS(3);
+#pragma unroll
+            for (int tc = 0; tc < MAXT; ++tc) {
+                sc[tc].x *= inv; sc[tc].y *= inv; sc[tc].z *= inv; sc[tc].w *= inv;
+                if (16 * tc + 16 <= Le) put(tc, sc[tc]);                  // (wave-uniform)
+                else if (16 * tc < Le) put_tail(tc, sc[tc]);
+            }
+            PROFS(7);
+#pragma unroll
+            for (int n = 0; n < NTC; ++n) O[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            nest_p<0, MAXT / 2>(steps, [&](auto is) __attribute__((always_inline)) {
+                constexpr int st = decltype(is)::value;
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (st + 1 < MAXT / 2) loadvp(min(st + 1, steps - 1), 0, (st & 1) ? va : wa);   // unconditional (the last step re-reads itself)
+                pv_mma(st, sc[2 * st], sc[2 * st + 1], (st & 1) ? wa : va, vc, [&]() __attribute__((always_inline)) {
+                    if constexpr (st + 1 < MAXT / 2) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        loadvp(min(st + 1, steps - 1), 1, vc);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                });
+            });
         }
     } else {
     const float* vbase = a.proj + rowb * a.ldp + OFF_KV + h * 2 * C + C + 4 * r;
@@ -1092,7 +1183,7 @@ __global__ __launch_bounds__(512) void ipa_scores_kernel(pf_ipa_attn_args a, int
     }
     PROFS(4);
     // D layout: lane (r = column, g), register e -> query 4 g + e
-    float* opt = SW + (size_t)wave * 16 * SLD;                   // (the wave's score region is dead now)
+    float* opt = SW + (size_t)wave * 16 * (KSPLIT ? 36 : SLD);   // (the wave's score region is dead now; KSPLIT: this image is all the wave has in LDS)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int ti = 4 * g + e, i = min(i0 + ti, Le - 1);      // (duplicates of row Le - 1 store identical values)

@@ -103,7 +103,12 @@ def main():
                                "Round 8 (the k fragments of the keys-are-the-state form shared per sample: the KF instantiations without the pair phase lose "
                                "their k loads and stores in front of the first LDS-DMA issue, every instantiation gains one kernel argument): the GPU suite "
                                "with tests/test_gpu_fresh_process.py, the repeat-launch bitwise tests and tests/test_gpu_shared_keys.py at the final sources, "
-                               "outputs of cfg2 / cfg3 / cfg4 / f16@cfg4 byte-equal to the parent library (profiles/r08/README.md)",
+                               "outputs of cfg2 / cfg3 / cfg4 / f16@cfg4 byte-equal to the parent library (profiles/r08/README.md).  "
+                               "Round 9 (the instantiations without the pair phase keep their scores in registers, nested tile / step guards, three value "
+                               "operand sets; the instantiations with it were recompiled around the shared qk_tile / pv_mma helpers; the f16 kernels kept "
+                               "their hashes): the GPU suite with tests/test_gpu_fresh_process.py, the repeat-launch bitwise tests, "
+                               "tests/test_gpu_shared_keys.py and tests/test_gpu_scores_in_regs.py at the final sources, outputs of cfg2 / cfg3 / cfg4 / "
+                               "f16@cfg4 byte-equal to the parent library (profiles/r09/README.md)",
                "kernels": got}
         with open(PIN, "w") as f:
             json.dump(pin, f, indent=1, sort_keys=True)
