@@ -1258,6 +1258,46 @@ typedef struct {
 } pf_sidechain_compare_args;
 int pf_sidechain_compare_fwd(const pf_sidechain_compare_args* a, pf_stream_t stream);
 
+/* ---- hydrogen bonds and salt bridges (ABI 65, added entry point) -------------------------------------------------------------------
+ * pf_polar_fwd: directional hydrogen bonds and salt-bridge atom pairs between the heavy atoms of different residues of a batch of
+ * structures, with explicit partner lists; the conventions are listed in csrc/polar.hip.  Heavy-atom criteria written from the
+ * publications (Baker & Hubbard 1984, McDonald & Thornton 1994: donor-acceptor distance and antecedent angles; Barlow & Thornton 1983:
+ * N-O distance) and checked against a float64 restatement; NOT checked against HBPLUS, PLIP or Rosetta.  Slots 0 .. min(n_atoms, 15) - 1
+ * are read; an atom takes part where atom_mask is set and its type has the slot (antecedents[type][slot][0] >= 0: every heavy atom is
+ * bonded to another of its residue).  residue_index: consecutive residues of a chain differ by exactly 1.
+ *   hbonds_atom, salt_atom [B,N,15]            partners of the row atom (a participating atom that is not a query row: -1);
+ *   hbonds_atom_cross, salt_atom_cross         partners whose residue has another group byte;
+ *   hbond_partner, salt_partner [B,N,15,4]     residue * 15 + slot of the partners, ascending, the 4 lowest, padded with -1;
+ *   hbonds_residue, salt_residue [B,N] (and the _cross twins)   the sums over the slots of the row atoms.
+ * The four _cross outputs and group come together or not at all.  Every pair shows in both of its rows; query restricts the rows, not
+ * the partners.  work: [B,N,4] floats, no initialisation needed.  Two launches, no atomics, nothing pair-sized, one writer per
+ * output: bit-identical from run to run and independent of the rest of the batch.  N > PF_POLAR_MAX_N, n_atoms < 14, a cutoff that
+ * is not finite and positive or a cosine outside [-1, 1] -> PF_E_BADARG; B > 65535 -> PF_E_TOOLARGE. */
+#define PF_POLAR_MAX_N 512
+#define PF_POLAR_MAX_PARTNERS 4
+typedef struct {
+    const float* pos;                                               /* [B,N,n_atoms,3] */
+    const unsigned char* atom_mask;                                 /* [B,N,n_atoms] */
+    const int64_t* aa;                                              /* [B,N] */
+    const int64_t* residue_index;                                   /* [B,N] */
+    const unsigned char* group;                                     /* [B,N] optional */
+    const unsigned char* query;                                     /* [B,N] optional */
+    const unsigned char* types;                                     /* [21,15] bit 1 donor, bit 2 acceptor */
+    const unsigned char* charge;                                    /* [21,15] 0 none, 1 cation N, 2 anion O */
+    const signed char* antecedents;                                 /* [21,15,2] bonded slots of the residue, -1: none */
+    float* work;                                                    /* [B,N,4] */
+    int* hbonds_atom; int* salt_atom;                               /* [B,N,15] */
+    int* hbonds_atom_cross; int* salt_atom_cross;                   /* [B,N,15] optional */
+    int* hbond_partner; int* salt_partner;                          /* [B,N,15,4] */
+    int* hbonds_residue; int* salt_residue;                         /* [B,N] */
+    int* hbonds_residue_cross; int* salt_residue_cross;             /* [B,N] optional */
+    int B, N, n_atoms;
+    float d_max;                                                    /* > 0; 3.5 */
+    float cos_acc, cos_don;                                         /* cosines of the smallest angles at the acceptor / donor; 0 */
+    float salt_max;                                                 /* > 0; 4.0 */
+} pf_polar_args;
+int pf_polar_fwd(const pf_polar_args* a, pf_stream_t stream);
+
 /* ---- lDDT and interface contacts (ABI 64, added entry points) ------------------------------------------------------------------
  * Both take the work-list family of pf_sidechain_compare_fwd: pair p = (i, j) of pairs [P,2] looks at the model x[i] and the reference
  * structure y[j] (y may alias x); group / query [By,N] belong to y; a pair with an index out of range gives zeros (min_dist: +inf).

@@ -246,6 +246,15 @@ class SidechainCompareArgs(C.Structure):
                 ("Bx", _i), ("By", _i), ("N", _i), ("P", _i), ("n_atoms_x", _i), ("n_atoms_y", _i), ("correct_tol", C.c_float)]
 
 
+class PolarArgs(C.Structure):
+    _fields_ = [("pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("residue_index", _fp), ("group", _fp), ("query", _fp), ("types", _fp),
+                ("charge", _fp), ("antecedents", _fp), ("work", _fp), ("hbonds_atom", _fp), ("salt_atom", _fp),
+                ("hbonds_atom_cross", _fp), ("salt_atom_cross", _fp), ("hbond_partner", _fp), ("salt_partner", _fp),
+                ("hbonds_residue", _fp), ("salt_residue", _fp), ("hbonds_residue_cross", _fp), ("salt_residue_cross", _fp),
+                ("B", _i), ("N", _i), ("n_atoms", _i), ("d_max", C.c_float), ("cos_acc", C.c_float), ("cos_don", C.c_float),
+                ("salt_max", C.c_float)]
+
+
 class LddtArgs(C.Structure):
     _fields_ = [("pos_x", _fp), ("pos_y", _fp), ("mask_x", _fp), ("mask_y", _fp), ("aa_x", _fp), ("aa_y", _fp), ("pairs", _fp),
                 ("group", _fp), ("query", _fp), ("scored", _fp), ("kept", _fp), ("scored_cross", _fp), ("kept_cross", _fp),
@@ -392,6 +401,7 @@ _SIGNATURES = {
     "pf_cavity_work_bytes": ([_i, _i, _i], _i),
     "pf_torsions_fwd": ([C.POINTER(TorsionsArgs), _fp], _i),
     "pf_sidechain_compare_fwd": ([C.POINTER(SidechainCompareArgs), _fp], _i),
+    "pf_polar_fwd": ([C.POINTER(PolarArgs), _fp], _i),
     "pf_lddt_fwd": ([C.POINTER(LddtArgs), _fp], _i),
     "pf_contacts_fwd": ([C.POINTER(ContactsArgs), _fp], _i),
     "pf_cluster_fwd": ([C.POINTER(ClusterArgs), _fp], _i),

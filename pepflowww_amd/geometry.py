@@ -5,7 +5,7 @@ Input families, one binding path each:
   pair work lists   point sets x [Bx,N,3] / y [By,N,3] with masks and `pairs` [P,2] -- `_pair_inputs`: superpose (and align, batch_align,
                     superpose_rmsd), tm_score, tm_align and their pairwise_* matrices (`_within_groups`, `_mirrored`);
   heavy-atom structures   pos [B,N,A,3], atom_mask [B,N,A] and per-residue [B,N] tensors -- `_structure`: structural_violations, sasa,
-                    torsion_angles, interface_energy and each side of sidechain_compare (dssp reads the same pos with a residue mask);
+                    torsion_angles, interface_energy, polar_interactions and each side of sidechain_compare (dssp reads the same pos with a residue mask);
                     cavity_scan (pf_cavity_fwd: buriedness scan, cavities and lining residues of whole receptors, N <= 4096) too;
   both at once      two heavy-atom structure sets and a work list -- `_structure_pairs`: lddt (pf_lddt_fwd, the values of OpenFold's
                     lddt / lddt_ca, openfold/utils/loss.py:382-458) and interface_contacts (pf_contacts_fwd), which dockq combines
@@ -1098,6 +1098,120 @@ def interface_energy(pos, atom_mask, aa, group, query=None, cutoff=8.0, weights=
     half = 0.5 if query is None else 1.0
     out["terms"] = out["terms_residue"].double().sum(1) * half
     out["energy"] = out["energy_residue"].double().sum(1) * half
+    return out
+
+
+# ---- hydrogen bonds and salt bridges ---------------------------------------------------------------------------------------------------
+# Heavy-atom criteria by the published conventions: donor-acceptor distance and antecedent angles (Baker & Hubbard 1984, McDonald &
+# Thornton 1994), N-O distance of a salt bridge (Barlow & Thornton 1983).  Written from the publications and checked against a float64
+# restatement (tests/polar_oracle.py) and constructed cases; NOT checked against HBPLUS, PLIP or Rosetta.
+POLAR_MAX_N = 512           # PF_POLAR_MAX_N
+POLAR_SLOTS = 15
+POLAR_MAX_PARTNERS = 4      # PF_POLAR_MAX_PARTNERS
+CHARGE_CATION, CHARGE_ANION = 1, 2
+CATION_NITROGENS = {"LYS": ("NZ",), "ARG": ("NE", "NH1", "NH2")}
+HIS_CATION_NITROGENS = ("ND1", "NE2")       # only with his_charged
+ANION_OXYGENS = {"ASP": ("OD1", "OD2"), "GLU": ("OE1", "OE2")}
+
+
+def charge_table(his_charged=False):
+    """-> [21,15] uint8 CPU tensor: the charge class of heavy-atom slot s of residue type t, by atom name in the package's own table:
+    CHARGE_CATION (1) for Lys NZ and Arg NE / NH1 / NH2 (with `his_charged` also His ND1 / NE2), CHARGE_ANION (2) for Asp OD1 / OD2
+    and Glu OE1 / OE2, 0 elsewhere.  The termini carry no charge here.  Row 20 (any type outside 0..19): none."""
+    from .preprocess import _tables
+    t = _tables()
+    tab = torch.zeros(21, POLAR_SLOTS, dtype=torch.uint8)
+    cations = dict(CATION_NITROGENS, **({"HIS": HIS_CATION_NITROGENS} if his_charged else {}))
+    for cls, by_res in ((CHARGE_CATION, cations), (CHARGE_ANION, ANION_OXYGENS)):
+        for res, atoms in by_res.items():
+            r = t["res_index"][res]
+            for nm in atoms:
+                tab[r, list(t["atom_names"][r][:POLAR_SLOTS]).index(nm)] = cls
+    return tab
+
+
+def antecedent_table():
+    """-> [21,15,2] int8 CPU tensor: the slots of the heavy atoms bonded to slot s inside a residue of type t (`bond_table`), the two
+    lowest in ascending order, -1 for none.  Every heavy atom is bonded to another of its residue, so [t,s,0] >= 0 exactly where the
+    type has the slot.  No donor, acceptor or charged atom has more than two bonded heavy atoms in its residue (only carbons and
+    proline's N lose a neighbour here); the peptide bond's C of the previous residue is added to N by the kernel."""
+    bonds = bond_table()
+    tab = torch.full((21, POLAR_SLOTS, 2), -1, dtype=torch.int8)
+    for t in range(21):
+        for s in range(POLAR_SLOTS):
+            for k, v in enumerate(torch.nonzero(bonds[t, s]).flatten().tolist()[:2]):
+                tab[t, s, k] = v
+    return tab
+
+
+def _cosine(name, degrees):
+    try:
+        v = float(degrees)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not 0.0 <= v <= 180.0:
+        raise ValueError(f"{name} must be an angle of 0 to 180 degrees, got {degrees!r}")
+    return math.cos(math.radians(v))
+
+
+def polar_interactions(pos, atom_mask, aa, residue_index, group=None, query=None, d_max=3.5, acc_angle_min=90.0, don_angle_min=90.0,
+                       salt_max=4.0, his_charged=False):
+    """pf_polar_fwd: directional hydrogen bonds and salt-bridge atom pairs between the heavy atoms of different residues, with the
+    explicit list of which atom bonds which (conventions: csrc/polar.hip).  Heavy atoms only, by the published conventions: donor-
+    acceptor distance and antecedent angles (Baker & Hubbard 1984, McDonald & Thornton 1994) and the N-O distance of a salt bridge
+    (Barlow & Thornton 1983).  It is written from the publications and checked against a float64 restatement in this tree and against
+    constructed cases; it has not been checked against HBPLUS, PLIP or Rosetta, and it is none of their outputs (no hydrogens are
+    placed, histidine's tautomer is unknown, no water, no terminal charges).
+
+    pos [B,N,A,3] heavy atoms in the package's order, A >= 14, slots 0 .. min(A,15)-1 are read; atom_mask [B,N,A]; aa [B,N] residue
+    types; residue_index [B,N] (required; metrics.residue_index): consecutive residues of a chain differ by exactly 1; N <= 512.  An
+    atom takes part where its mask is set and its type has the slot.  Donors and acceptors: `interface_type_table`; the antecedents
+    of an atom: the participating atoms bonded to it in its residue (`antecedent_table`) and, for a backbone N, the C of the
+    chain-consecutive previous row.  A hydrogen bond joins atoms of different residues, one a donor D and the other an acceptor A (both
+    assignments are tried, either passing counts once), with |D - A| <= d_max, every angle X-A...D >= acc_angle_min over the
+    antecedents X of A and every angle Y-D...A >= don_angle_min over the antecedents Y of D (degrees; an atom without an antecedent
+    passes); the backbone N of residue i never bonds O or OXT of the chain-consecutive residue i - 1.  A salt bridge is a cation N
+    and an anion O (`charge_table`; histidine's ring nitrogens only with his_charged) of different residues with |N - O| <=
+    salt_max, whether or not they are hydrogen bonded.  query [B,N] (optional): only atoms of query residues are rows, every
+    participating atom is still a partner; a participating atom that is not a row has counts -1 and empty lists.  group [B,N]
+    (optional) adds the *_cross outputs: the partners whose residue has another group byte.
+    -> dict of device tensors: hbonds_atom, salt_atom [B,N,15] int32 (partners per row atom); hbond_partner, salt_partner [B,N,15,4]
+    int32 (residue * 15 + slot of the partners, ascending, the 4 lowest, -1 padded; the counts stay exact); hbonds_residue,
+    salt_residue [B,N] int32; n_hbonds, n_salt_bridges [B] int64: each pair shows in both of its rows, so these are HALF the row sums
+    -- with `query` the plain sums over the query rows.  With `group` every key also with `_cross` appended."""
+    d_max, salt_max = _positive("d_max", d_max), _positive("salt_max", salt_max)
+    cos_acc, cos_don = _cosine("acc_angle_min", acc_angle_min), _cosine("don_angle_min", don_angle_min)
+    if residue_index is None:
+        raise ValueError("polar_interactions needs `residue_index` [B,N] (metrics.residue_index): it tells which rows are bonded")
+    dev, (B, N, A), pos, atom_mask, (aa, residue_index, group, query) = _structure(pos, atom_mask, (
+        ("aa", aa, torch.int64), ("residue_index", residue_index, torch.int64), ("group", group, torch.uint8),
+        ("query", query, torch.uint8)), max_n=POLAR_MAX_N)
+    a = _capi.PolarArgs()
+    _bind_in(a, pos=pos, atom_mask=atom_mask, aa=aa, residue_index=residue_index, group=group, query=query)
+    S, K = POLAR_SLOTS, POLAR_MAX_PARTNERS
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)  # noqa: E731
+    out = {"hbonds_atom": i32(B, N, S), "salt_atom": i32(B, N, S), "hbond_partner": i32(B, N, S, K), "salt_partner": i32(B, N, S, K),
+           "hbonds_residue": i32(B, N), "salt_residue": i32(B, N)}
+    if group is not None:
+        out.update(hbonds_atom_cross=i32(B, N, S), salt_atom_cross=i32(B, N, S), hbonds_residue_cross=i32(B, N),
+                   salt_residue_cross=i32(B, N))
+    if B and N:
+        a.types = _table("interface_types", dev, interface_type_table).data_ptr()
+        a.charge = _table("charge", dev, lambda: charge_table(his_charged), bool(his_charged)).data_ptr()
+        a.antecedents = _table("antecedents", dev, antecedent_table).data_ptr()
+        _bind_out(a, out)
+        work = torch.empty(B, N, 4, device=dev)     # the residue-sized workspace: centre and extent
+        a.work = work.data_ptr()
+        a.B, a.N, a.n_atoms = B, N, A
+        a.d_max, a.cos_acc, a.cos_don, a.salt_max = d_max, cos_acc, cos_don, salt_max
+        _capi.check(_capi.load().pf_polar_fwd(C.byref(a), _capi.stream_ptr()), "pf_polar_fwd")
+    else:
+        for k, v in out.items():
+            v.fill_(-1) if k.endswith("_partner") else v.zero_()
+    div = 2 if query is None else 1
+    for tag in ("", "_cross") if group is not None else ("",):
+        out["n_hbonds" + tag] = out["hbonds_residue" + tag].sum(1, dtype=torch.int64) // div
+        out["n_salt_bridges" + tag] = out["salt_residue" + tag].sum(1, dtype=torch.int64) // div
     return out
 
 

@@ -9,7 +9,9 @@ side-chain packing table, chi1-chi4 errors against the native and the share of r
 (`sidechain_packing`); superposition-free local accuracy, lDDT with the values of OpenFold's lddt / lddt_ca
 (openfold/utils/loss.py:382-458), over the peptide and across the interface (`local_accuracy`); docking quality, Fnat, iRMSD, LRMSD and
 DockQ (`docking_quality`); an empirical peptide-receptor interface energy, the functional form of AutoDock Vina's scoring function
-written from the publication and not checked against that program (`binding_energy`); structural clusters of the samples of each
+written from the publication and not checked against that program (`binding_energy`); directional hydrogen bonds and salt bridges
+across the interface and the buried polar atoms without a hydrogen-bond partner, heavy-atom criteria written from the publications and
+not checked against HBPLUS, PLIP or Rosetta (`polar_satisfaction`); structural clusters of the samples of each
 complex, their representatives and the best-scored member of each (`cluster_samples`: gromos clustering after Daura et al. 1999, which
 follows the publication and is not checked against GROMACS, and single / complete / average linkage cut at a height, checked against
 scipy's fcluster(criterion="distance") as partitions only); rotamer side chains for a backbone-only sample, a staggered rotamer grid
@@ -17,7 +19,7 @@ scored with the interface energy's pair function and chosen by iterated conditio
 packer and takes their place in role only (`pack_samples`, and backbone="packed" in the structure metrics).
 
 Every per-residue, per-point and per-atom-pair operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd /
-pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_relax_fwd / pf_cluster_fwd / pf_pack_sidechains_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
+pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_polar_fwd / pf_relax_fwd / pf_cluster_fwd / pf_pack_sidechains_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
@@ -567,6 +569,75 @@ def binding_energy(final, batch, backbone="full_atom", cutoff=8.0):
     out["energy_per_rot"] = out["energy"] / (1.0 + ROT_PENALTY * out["n_rot"].double())
     w, t = geometry.VINA_WEIGHTS, out["terms"]
     out["clashing"] = w[2] * t[:, 2] > (w[0] * t[:, 0] + w[1] * t[:, 1]).abs()
+    return out
+
+
+def _bonded_residue_pairs(partner, gen):
+    """hbond_partner [B,L,15,K] -> [B,L,L] bool: residues i, j of different sides (gen) joined by a listed hydrogen bond.  A bond is
+    in the list of both of its atoms, so one that an atom's list of the 4 lowest partners drops is still seen from the other row."""
+    B, L = gen.shape
+    res = torch.div(partner.clamp(min=0), geometry.POLAR_SLOTS, rounding_mode="floor").long().reshape(B, L, -1)
+    hits = torch.zeros(B, L, L, dtype=torch.int32, device=gen.device)
+    hits.scatter_add_(2, res, (partner >= 0).reshape(B, L, -1).to(torch.int32))        # integer sums: the same from run to run
+    pairs = hits > 0
+    pairs = pairs | pairs.transpose(1, 2)
+    return pairs & (gen[:, :, None] != gen[:, None, :])
+
+
+def polar_satisfaction(final, batch, backbone="full_atom", max_sasa=1.0, probe_radius=1.4, n_points=960, **criteria):
+    """Polar chemistry at the interface of each sample's complex and of its native: directional hydrogen bonds and salt bridges
+    between peptide and receptor (geometry.polar_interactions) and the polar atoms buried at the interface without a hydrogen-bond
+    partner (joined with geometry.sasa), the filter that the reference's evaluation takes from Rosetta's interface analysis
+    (hbonds_int, delta_unsatHbonds).  Heavy atoms only, by the published heavy-atom conventions (Baker & Hubbard 1984, McDonald &
+    Thornton 1994, Barlow & Thornton 1983), written from the publications and checked against a float64 restatement in this tree; it
+    is not checked against HBPLUS, PLIP or Rosetta and is not Rosetta's count.  final / batch and the two complexes are those of
+    `structural_violations`; group = generate_mask & res_mask; one polar_interactions call and one sasa call per complex; `criteria`
+    (d_max, acc_angle_min, don_angle_min, salt_max, his_charged) go to polar_interactions.  With backbone="frames" the sample's
+    generated residues have N, CA, C, O only: it then reports the backbone's polar atoms only, which the native (with its side
+    chains) is not comparable with.
+
+    A polar atom is a participating donor or acceptor (geometry.interface_type_table).  It is buried when its accessible area in the
+    complex is <= max_sasa, and unsatisfied when it has no hydrogen bond at all (hbonds_atom == 0).  max_sasa = 1.0 A^2 is a starting
+    value, not a tuned one.  The interface holds the peptide and the receptor residues that bury more than 1 A^2, as in
+    `interface_area`.
+
+    -> dict of device tensors.  Per sample [B], int64:
+      n_hbonds_interface, n_salt_bridges_interface   hydrogen bonds / salt-bridge atom pairs between peptide and receptor;
+      n_hbonds_peptide       hydrogen bonds with both atoms in the peptide;
+      n_buried_unsat         buried unsatisfied polar atoms of the interface;
+      n_buried_unsat_delta   those of them that are exposed (area > max_sasa) in their own side alone: buried by binding;
+    hbond_recovery [B] float64: |P_sample & P_native| / (|P_native| + 1e-10) over the residue pairs P joined by a hydrogen bond
+    across the interface.  Per residue [B,L] int32: buried_unsat.  Every key also with `_native` appended (the native's
+    hbond_recovery is that of the native against itself)."""
+    max_sasa = float(max_sasa)
+    if not max_sasa >= 0.0:
+        raise ValueError(f"max_sasa must be >= 0, got {max_sasa}")
+    dev, res_mask, gen, index, sample, native = _complexes(final, batch, backbone, index=True)
+    rec = res_mask & ~gen
+    types = geometry._table("interface_types", dev, geometry.interface_type_table)
+    S = geometry.POLAR_SLOTS
+    out, bonded = {}, {}
+    for tag, (pos, mask, aa) in (("", sample), ("_native", native)):
+        mask = mask & res_mask[:, :, None]
+        p = geometry.polar_interactions(pos, mask, aa, index, group=gen, **criteria)
+        v = geometry.sasa(pos, mask, aa, group=gen, probe_radius=probe_radius, n_points=n_points)
+        bits = types[torch.where((aa < 0) | (aa > 19), 20, aa)]
+        part = torch.zeros_like(bits, dtype=torch.bool)
+        part[:, :, :mask.shape[2]] = mask[:, :, :S]
+        polar = ((bits & (geometry.TYPE_DONOR | geometry.TYPE_ACCEPTOR)) != 0) & part
+        face = (v["sasa_atom_own"].double() - v["sasa_atom"].double()).sum(-1) > 1.0
+        scope = gen | (face & rec)
+        unsat = polar & (v["sasa_atom"] <= max_sasa) & (p["hbonds_atom"] == 0) & scope[:, :, None]
+        delta = unsat & (v["sasa_atom_own"] > max_sasa)
+        inner = ((p["hbonds_atom"] - p["hbonds_atom_cross"]).sum(-1, dtype=torch.int64) * gen).sum(1) // 2
+        bonded[tag] = _bonded_residue_pairs(p["hbond_partner"], gen)
+        res = {"n_hbonds_interface": p["n_hbonds_cross"], "n_salt_bridges_interface": p["n_salt_bridges_cross"],
+               "n_hbonds_peptide": inner, "n_buried_unsat": unsat.sum((1, 2)), "n_buried_unsat_delta": delta.sum((1, 2)),
+               "buried_unsat": unsat.sum(-1, dtype=torch.int32)}
+        out.update({k + tag: t for k, t in res.items()})
+    n_native = bonded["_native"].sum((1, 2)).double() / 2
+    out["hbond_recovery"] = (bonded[""] & bonded["_native"]).sum((1, 2)).double() / 2 / (n_native + 1e-10)
+    out["hbond_recovery_native"] = n_native / (n_native + 1e-10)
     return out
 
 
