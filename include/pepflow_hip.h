@@ -622,6 +622,56 @@ typedef struct {
 } pf_guidance_args;
 int pf_guidance_fwd(const pf_guidance_args* a, pf_stream_t stream);
 
+/* ---- tempered and stochastic sampling: sequence temperature and noise on the backbone state (csrc/temper.hip) ----------
+ * The reference has NO such call: its sample() draws every residue type at temperature 1 and integrates the rotation and translation
+ * tracks as a deterministic Euler ODE.  The trained flow has never seen a perturbed state: an off-label use, like the partial start and
+ * the guidance.  Nothing was tuned on a trained checkpoint.
+ * One launch per step, after the network (and after pf_guidance_fwd) and before pf_sampler_step*; one thread per row.  With
+ * s = step[0] it returns without writing when s >= num_steps, as pf_sampler_step does.  Two independent parts:
+ *  a) tau != NULL, every step, the last one included: tempered_logits[row,k] = pred_logits[row,k] / tau[row] for all 20 classes of every
+ *     row (a true division: tau = 1 gives back the input's bits).  The caller points pf_sampler_args.pred_logits at tempered_logits, so
+ *     only the PREDICTION draw (draw index 1 + 2s: the recorded sequence and the torsion mask) is tempered; the initial draw and the
+ *     state draw from simplex_t are the interpolant's and stay as they are.  tau == NULL: nothing is written.
+ *  b) params != NULL, only when s < num_steps - 1: Euler-Maruyama noise on the rows with gen_mask > 0.5 whose backbone flag is on
+ *     (res_flags bit 0 when the plane is given, sample_bb otherwise: the rule of pf_sampler_step_cond).  t = ts[s], dt = ts[s+1] - ts[s],
+ *     a = sqrtf(dt) * (1 - t)^power for t < t_off, 0 otherwise (power 0, 1 or 2, by multiplication), z = six standard normals of the row:
+ *       trans_t += (sigma_trans * a) * z[0:3]              (Angstrom per sqrt of flow time)
+ *       rot_t    = rot_t * Exp((sigma_rot * a) * z[3:6])   (radian per sqrt of flow time; a Gaussian in the tangent space, NOT IGSO3)
+ *     A part whose scale is 0 leaves its tensor's bits.  The step kernel then takes its Euler step from the perturbed state ("perturb,
+ *     then drift").  No other row and no other tensor (trans0, simplex_t, ang_t, seq_t) is touched.
+ * z: gauss != NULL -> caller-supplied [num_steps-1,B,L,6]; NULL -> Philox4x32-10 with the sampler's key (seed / seed_dev / sample_ids /
+ * first_sample exactly as pf_sampler_args), counter {l*2 + q, 0x80000000 | s, lo32(gs), hi32(gs)} for q in {0, 1} (the categorical
+ * draws use counter[1] < 2*num_steps + 1: the high bit keeps the streams apart), uniforms u = ((c >> 8) + 0.5) * 2^-24, Box-Muller
+ * r = sqrtf(-2 logf(u_a)), (r cosf(2 pi u_b), r sinf(2 pi u_b)) on the pairs (u0,u1), (u2,u3) of block 0 and (u0,u1) of block 1.
+ * params (device float [PF_TEMPER_NPARAMS]): sigma_trans sigma_rot power t_off 0 0 0 0, read at run time: a captured graph serves
+ * later calls that rewrite the buffer.
+ * PF_E_BADARG: a NULL struct, step or ts, sizes <= 0; neither tau nor params (nothing to do); tau without pred_logits / tempered_logits;
+ * params without rot_t / trans_t / gen_mask; gauss without params. */
+#define PF_TEMPER_NPARAMS 8
+typedef struct {
+    /* logits */
+    const float* pred_logits;      /* [B*L,20] the network's logits */
+    float* tempered_logits;        /* [B*L,20] required with tau */
+    const float* tau;              /* optional [B*L] temperature of the row, > 0 */
+    /* state */
+    float* rot_t;                  /* [B*L,9] */
+    float* trans_t;                /* [B*L,3] */
+    const float* gen_mask;         /* [B*L] 1 = generated residue */
+    const uint8_t* res_flags;      /* optional [B*L]: bit 0 = backbone flag of the row (pf_sampler_cond_args.res_flags) */
+    /* time */
+    const float* ts;               /* time grid [num_steps] */
+    const int* step;               /* device step counter (pf_sampler_args.step) */
+    /* noise */
+    const float* params;           /* optional [PF_TEMPER_NPARAMS]; NULL = no noise */
+    const float* gauss;            /* optional [num_steps-1,B*L,6] standard normals; NULL = in-kernel Philox */
+    const uint64_t* seed_dev;      /* optional, as pf_sampler_args.seed_dev */
+    const int64_t* sample_ids;     /* optional [B], as pf_sampler_args.sample_ids */
+    uint64_t seed;
+    int64_t first_sample;
+    int B, L, num_steps, sample_bb;
+} pf_sampler_temper_args;
+int pf_sampler_temper(const pf_sampler_temper_args* a, pf_stream_t stream);
+
 /* stand-alone manifold steps (KAT surface): so3_utils.geodesic_t (500-520) and torus.tor_geodesic_t */
 int pf_so3_geodesic(const float* base, const float* target, const float* t, float* out, int n, pf_stream_t stream);
 int pf_so3_log(const float* rot, float* rotvec, int n, pf_stream_t stream);

@@ -18,6 +18,8 @@ _fp = C.c_void_p
 _i = C.c_int
 # include/pepflow_hip.h, guided sampling
 GUIDE_MAX_PAIRS, GUIDE_MAX_L, GUIDE_NPARAMS, GUIDE_NTERMS = 64, 1024, 16, 5
+# include/pepflow_hip.h, tempered and stochastic sampling
+TEMPER_NPARAMS = 8
 
 
 class LinearArgs(C.Structure):
@@ -92,6 +94,12 @@ class GuidanceArgs(C.Structure):
                 ("pair_idx", _fp), ("pair_par", _fp), ("params", _fp), ("ts", _fp), ("step", _fp), ("t", _fp),
                 ("guided_trans", _fp), ("energy", _fp), ("shift_max", _fp), ("grad", _fp), ("error", _fp),
                 ("B", _i), ("L", _i), ("num_steps", _i), ("sample_bb", _i)]
+
+
+class SamplerTemperArgs(C.Structure):
+    _fields_ = [("pred_logits", _fp), ("tempered_logits", _fp), ("tau", _fp), ("rot_t", _fp), ("trans_t", _fp), ("gen_mask", _fp),
+                ("res_flags", _fp), ("ts", _fp), ("step", _fp), ("params", _fp), ("gauss", _fp), ("seed_dev", _fp), ("sample_ids", _fp),
+                ("seed", C.c_uint64), ("first_sample", C.c_int64), ("B", _i), ("L", _i), ("num_steps", _i), ("sample_bb", _i)]
 
 
 class TrainArgs(C.Structure):
@@ -345,6 +353,7 @@ _SIGNATURES = {
     "pf_sampler_init_cond": ([C.POINTER(SamplerArgs), C.POINTER(SamplerCondArgs), _fp, _fp, _fp, _fp, _fp], _i),
     "pf_sampler_step_cond": ([C.POINTER(SamplerArgs), C.POINTER(SamplerCondArgs), _fp], _i),
     "pf_guidance_fwd": ([C.POINTER(GuidanceArgs), _fp], _i),
+    "pf_sampler_temper": ([C.POINTER(SamplerTemperArgs), _fp], _i),
     "pf_train_corrupt_fwd": ([C.POINTER(TrainArgs), _fp], _i),
     "pf_train_losses_fwd": ([C.POINTER(TrainArgs), _fp], _i),
     "pf_train_losses_bwd": ([C.POINTER(TrainArgs), C.POINTER(TrainBwdArgs), _fp], _i),

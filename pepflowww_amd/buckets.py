@@ -90,12 +90,12 @@ def sub_noise(noise, idx, L0, Lk):
     for k, v in noise.items():
         if v is None:
             out[k] = None
-        elif k == "expo":                                  # [2N, B, L0, 20]
+        elif k in ("expo", "gauss"):                       # [2N, B, L0, 20] / [N-1, B, L0, 6]: the sample on axis 1
             w = _rows(v, idx, axis=1)
             if Lk < L0:
                 w = w[:, :, :Lk].contiguous()
             elif Lk > L0:
-                w = _fit(w, L0, Lk, 2, 1.0)
+                w = _fit(w, L0, Lk, 2, 1.0 if k == "expo" else 0.0)
             out[k] = w
         elif k == "rot0":
             w = _fit(_rows(v, idx), L0, Lk, 1, 0)
@@ -114,6 +114,12 @@ def sub_guide(guide, idx, L0, Lk):
     Lk; residue indices stay (padding is appended at the end)."""
     from .sampler import fit_guide
     return fit_guide(guide, L0, Lk, idx)
+
+
+def sub_temper(temper, idx, L0, Lk):
+    """The packed tempering (sampler.make_temper) of the samples `idx`: their own temperature rows, the plane cut / padded to Lk."""
+    from .sampler import fit_temper
+    return fit_temper(temper, L0, Lk, idx)
 
 
 def sub_cond(cond, idx, L0, Lk):
@@ -140,12 +146,13 @@ class BucketedSampler:
         self._pad_rows = None
 
     # ---- set-up of one call ----------------------------------------------------------------------------------------------
-    def bind(self, batch, noise, L0, seed, first_sample, stamp=lambda name: None, grid=None, cond=None, guide=None):
+    def bind(self, batch, noise, L0, seed, first_sample, stamp=lambda name: None, grid=None, cond=None, guide=None, temper=None):
         """batch / noise: the caller's ([B, L0, ...], not padded).  Builds (or fetches from the encoder's cache) one engine + sampler
         per bucket, encodes each sub-batch into its engine's pair buffer and initialises the sampler states.  grid / cond: the call's
         time grid (None: the reference's) and packed conditioning (sampler.make_cond), sliced and padded per bucket like the noise;
         they stay in the samplers' own buffers, so the re-initialisation after the calibration probes is the conditioned one too.
-        guide: the call's packed guidance (sampler.make_guide), sliced per bucket the same way."""
+        guide: the call's packed guidance (sampler.make_guide), sliced per bucket the same way.
+        temper: the call's packed tempering (sampler.make_temper), likewise; the pre-drawn normals follow the samples with the noise."""
         if grid is None:
             from .sampler import make_grid
             grid = make_grid(self.N)
@@ -167,7 +174,7 @@ class BucketedSampler:
             stamp("encode")
             eng.bind_context(node, edge, sb["res_mask"])
             stamp("bind")
-            smp = eng.sampler(self.N, self.flags, cond=cond is not None, guide=guide is not None)
+            smp = eng.sampler(self.N, self.flags, cond=cond is not None, guide=guide is not None, temper=temper is not None)
             smp.set_seed(seed, first_sample)
             smp.set_grid(grid)
             ids = torch.as_tensor(idx, dtype=torch.int64) + int(first_sample)
@@ -177,6 +184,8 @@ class BucketedSampler:
                 smp.set_cond(sub_cond(cond, idx, L0, Lk), (R1, x1, ang1, seq1))
             if guide is not None:
                 smp.set_guide(sub_guide(guide, idx, L0, Lk))
+            if temper is not None:
+                smp.set_temper(sub_temper(temper, idx, L0, Lk))
             smp.init_state(nz)
             self._nz.append(nz)
             smp.L_out = Lk

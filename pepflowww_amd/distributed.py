@@ -47,7 +47,8 @@ def shard_batch(batch, world, rank):
 
 
 def shard_noise(noise, lo, hi):
-    return {k: (v[:, lo:hi] if k == "expo" else v[lo:hi]).contiguous() for k, v in noise.items() if v is not None}
+    """the pre-drawn noise of the samples [lo, hi): expo [2N, B, L, 20] and gauss [N-1, B, L, 6] carry the sample on axis 1"""
+    return {k: (v[:, lo:hi] if k in ("expo", "gauss") else v[lo:hi]).contiguous() for k, v in noise.items() if v is not None}
 
 
 def pack_state(step_dict):
@@ -175,10 +176,12 @@ def sample_sharded(model, batch, num_steps=100, *, noise=None, seed=None, group=
     nz = shard_noise(noise, lo, hi) if noise is not None else seeded_noise(lo, hi, L, seed)
     sizes = [shard_bounds(total, world, r)[1] - shard_bounds(total, world, r)[0] for r in range(world)]
     if hi > lo:
-        from .sampler import shard_cond_kwargs, shard_guide
+        from .sampler import shard_cond_kwargs, shard_guide, shard_temper
         kw = shard_cond_kwargs(kw, lo, hi, total)      # per-sample conditioning (row flags, allowed classes, start state): this shard's rows
         if kw.get("guide") is not None:
             kw["guide"] = shard_guide(kw["guide"], lo, hi, total)      # ... and this shard's hot spots and restraint lists
+        if kw.get("temper") is not None:
+            kw["temper"] = shard_temper(kw["temper"], lo, hi, total)    # ... and its temperature plane
         smp = model.sample(local, num_steps, noise=nz, seed=seed, first_sample=lo, return_sampler=True, **kw)
         packed = _final_state_of(smp)
     else:

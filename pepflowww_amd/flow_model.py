@@ -10,7 +10,7 @@ from torch import nn
 
 from . import _capi, featurize
 from .modules import EdgeEmbedder, GAEncoder, NodeEmbedder
-from .sampler import DeviceSampler, default_noise, fit_cond, fit_guide, make_cond, make_guide
+from .sampler import DeviceSampler, check_gauss, default_noise, fit_cond, fit_guide, fit_temper, make_cond, make_guide, make_temper
 from .train_forward import TrainForward, default_train_noise
 
 MAX_NUM_HEAVYATOMS = 15     # pepflow/modules/protein/constants.py:91
@@ -45,8 +45,8 @@ def _pad_residues(batch, noise, L0, L):
     for k, v in noise.items():
         if v is None:
             nz[k] = None
-        elif k == "expo":                                # [2N, B, L0, 20]; padded draws are never used (1.0 keeps p / E finite)
-            nz[k] = _pad_axis1(v.reshape((-1, L0) + tuple(v.shape[3:])), L - L0, 1.0).reshape(tuple(v.shape[:2]) + (L,) + tuple(v.shape[3:]))
+        elif k in ("expo", "gauss"):                     # [2N, B, L0, 20] / [N-1, B, L0, 6]; padded draws are never used (1.0 keeps p / E finite)
+            nz[k] = _pad_axis1(v.reshape((-1, L0) + tuple(v.shape[3:])), L - L0, 1.0 if k == "expo" else 0.0).reshape(tuple(v.shape[:2]) + (L,) + tuple(v.shape[3:]))
         elif k == "rot0":                                # [B, L0, 3, 3]: identity frames on the padding
             w = _pad_axis1(v, L - L0, 0)
             w[:, L0:, 0, 0] = 1
@@ -158,7 +158,7 @@ class FlowModel(nn.Module):
 
     def _sample_impl(self, batch, num_steps=100, sample_bb=True, sample_ang=True, sample_seq=True, *,
                noise=None, seed=None, first_sample=0, use_graph=True, return_sampler=False, timings=None, pageable=False, check_range=True,
-               buckets="auto", gc_collect=True, calibrate=True, t_start=None, ts=None, start=None, aa_allowed=None, guide=None, _gc_was_enabled=None):
+               buckets="auto", gc_collect=True, calibrate=True, t_start=None, ts=None, start=None, aa_allowed=None, guide=None, temper=None, _gc_was_enabled=None):
         """Reference signature + keyword-only extensions:
         t_start      the time grid becomes linspace(t_start, 1, num_steps) instead of linspace(1e-2, 1, num_steps); 0 < t_start < 1;
         ts           an explicit grid: num_steps strictly increasing values in (0, 1] (excludes t_start);
@@ -180,7 +180,15 @@ class FlowModel(nn.Module):
                      scale=1.0, t_on=0.0, power=1 (0, 1 or 2), max_shift=2.0 (Angstrom per step).  Afterwards `model.last_guidance` =
                      {"energy": [num_steps,B,5], "shift_max": [num_steps,B], "terms": names} (CPU tensors).  The reference has no
                      such call: an OFF-LABEL use of the trained flow, and the defaults are starting values, not tuned ones;
-        noise        dict(rot0, trans0, ang0, simplex0[, expo]) of pre-drawn noise (parity tests);
+        temper       None, or a dict that switches TEMPERED / STOCHASTIC sampling on (csrc/temper.hip; formulas: INTEGRATION.md).  Entries:
+                     seq_temperature=1.0 (a float > 0 or a tensor [L] / [B,L]: the prediction's logits are divided by it before the
+                     residue type is drawn), sigma_trans=0.0 (Angstrom per sqrt of flow time) and sigma_rot=0.0 (radian per sqrt of
+                     flow time): Euler-Maruyama noise of scale sigma * sqrt(dt) * (1 - t)^power on the translation and (as a
+                     tangent-space Gaussian) the rotation state of the generated residues whose backbone is sampled, on every step
+                     but the last; power=1 (0, 1 or 2), t_off=1.0 (no noise from that time on).  The reference has no such call: an
+                     OFF-LABEL use of the trained flow, and the defaults are starting values, not tuned ones;
+        noise        dict(rot0, trans0, ang0, simplex0[, expo][, gauss]) of pre-drawn noise (parity tests); gauss [num_steps-1,B,L,6]:
+                     the normals of the state noise -- required beside expo when temper has a non-zero sigma (else drawn on the device);
         seed         Philox seed for the in-kernel categorical draws (default: from torch's CPU generator); with noise=None an
                      explicit seed also keys the initial noise per GLOBAL sample index (distributed.seeded_noise);
         first_sample global index of this shard's first sample (world-size independent RNG streams);
@@ -224,6 +232,8 @@ class FlowModel(nn.Module):
         grid, flags, cond = make_cond(B, L0, num_steps, sample_bb, sample_ang, sample_seq, t_start, ts, start, aa_allowed)
         guide = make_guide(guide, B, L0, batch.get("generate_mask"), batch.get("res_mask"))
         self.last_guidance = None                      # the per-step energies and largest shifts of a guided call
+        temper = make_temper(temper, B, L0)
+        check_gauss(noise, temper, int(num_steps), B, L0)
         if noise is None:
             if seed is None:
                 noise = default_noise(B, L0)          # torch's global CPU generator, like the reference (flow_model.py:252-277)
@@ -237,7 +247,7 @@ class FlowModel(nn.Module):
             if len(plan) > 1:
                 return self._sample_bucketed(plan, batch, num_steps, flags, noise, seed, first_sample,
                                              use_graph, return_sampler, timings, pageable, check_range, stamp, gc_collect, calibrate, _gc_was_enabled,
-                                             grid=grid, cond=cond, guide=guide)
+                                             grid=grid, cond=cond, guide=guide, temper=temper)
         # Residue axis padded to a multiple of 16 internally (what PaddingCollate does to a shorter sample of a batch: pad values,
         # res_mask False -- padded residues are inert, tests/test_gpu_parity.py ragged cases): every kernel then runs its
         # full-tile path (16-row / 16-key tiles, float4 rows of the [B,8,L,L] buffers).  In-kernel random draws are keyed by
@@ -247,6 +257,7 @@ class FlowModel(nn.Module):
             batch, noise = _pad_residues(batch, noise, L0, L)
             cond = fit_cond(cond, L0, L)
             guide = fit_guide(guide, L0, L)
+            temper = fit_temper(temper, L0, L)
         stamp("noise")
         # The engine (workspaces, launch plan), its sampler (trajectory buffers, captured graphs) and the packed weights are cached
         # (GAEncoder.engine / DenoiseEngine.sampler): a second call at a shape seen before only encodes, binds and replays.
@@ -258,7 +269,7 @@ class FlowModel(nn.Module):
         stamp("bind")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        smp = eng.sampler(num_steps, flags, cond=cond is not None, guide=guide is not None)
+        smp = eng.sampler(num_steps, flags, cond=cond is not None, guide=guide is not None, temper=temper is not None)
         smp.set_seed(seed, first_sample)
         smp.set_grid(grid)
         smp.set_context(R1, x1, ang1, seq1, batch["generate_mask"])
@@ -266,6 +277,8 @@ class FlowModel(nn.Module):
             smp.set_cond(cond, (R1, x1, ang1, seq1))
         if guide is not None:
             smp.set_guide(guide)
+        if temper is not None:
+            smp.set_temper(temper)
         smp.init_state(noise)
         stamp("setup")
         if use_graph and timings is not None and smp.needs_capture():
@@ -304,10 +317,11 @@ class FlowModel(nn.Module):
         return traj
 
     def _sample_bucketed(self, plan, batch, num_steps, flags, noise, seed, first_sample, use_graph, return_sampler, timings, pageable,
-                         check_range, stamp, gc_collect=True, calibrate=True, _gc_was_enabled=None, grid=None, cond=None, guide=None):
+                         check_range, stamp, gc_collect=True, calibrate=True, _gc_was_enabled=None, grid=None, cond=None, guide=None,
+                         temper=None):
         """sample() of a ragged batch through its length buckets (pepflowww_amd/buckets.py): same inputs, noise, Philox streams and
-        output format as the unsplit path.  grid / cond / guide: the call's time grid, packed conditioning (sampler.make_cond) and
-        packed guidance (sampler.make_guide)."""
+        output format as the unsplit path.  grid / cond / guide / temper: the call's time grid, packed conditioning (sampler.make_cond),
+        packed guidance (sampler.make_guide) and packed tempering (sampler.make_temper)."""
         from .buckets import BucketedSampler
         stamp("noise")
         B, L0 = batch["aa"].shape
@@ -316,7 +330,7 @@ class FlowModel(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         smp = BucketedSampler(self, plan, B, L, num_steps, flags)
         smp.calibrate = bool(calibrate)
-        smp.bind(batch, noise, L0, seed, first_sample, stamp, grid=grid, cond=cond, guide=guide)
+        smp.bind(batch, noise, L0, seed, first_sample, stamp, grid=grid, cond=cond, guide=guide, temper=temper)
         if use_graph and timings is not None and smp.needs_capture():
             smp.capture()
             stamp("capture")

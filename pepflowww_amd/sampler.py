@@ -11,6 +11,7 @@ rebuilds `t` on the host every step (288).  Here the whole loop lives on the GPU
 """
 import ctypes as C
 import math
+import numbers
 
 import numpy as np
 import torch
@@ -342,12 +343,103 @@ def shard_guide(guide, lo, hi, total):
     return out
 
 
-class DeviceSampler:
-    """Owned by its engine (DenoiseEngine.sampler caches one per (num_steps, flags, cond, guide)): trajectory buffers and the captured
-    graphs are reused by the next sample() call; set_seed() / set_grid() / set_context() / set_cond() / set_guide() / init_state() are
-    what a call changes."""
+# ---- tempered and stochastic sampling: host-side validation and packing (no GPU needed) ------------------------------------------
+# A temperature on the prediction's sequence draw and Euler-Maruyama noise on the rotation and translation state (csrc/temper.hip;
+# formulas: include/pepflow_hip.h and INTEGRATION.md).  The reference has none of this: like the partial start and the guidance an
+# OFF-LABEL use of the trained flow.  The defaults are starting values: nothing has been tuned on a trained checkpoint.
+TEMPER_DEFAULTS = {"seq_temperature": 1.0, "sigma_trans": 0.0, "sigma_rot": 0.0, "power": 1, "t_off": 1.0}
+_TEMPER_SLOTS = ("sigma_trans", "sigma_rot", "power", "t_off")      # slots of the device parameter vector (pf_sampler_temper_args.params)
 
-    def __init__(self, engine, num_steps, flags=(True, True, True), first_sample=0, seed=0, cond=False, guide=False):
+
+def make_temper(temper, B, L):
+    """sample()'s `temper` dict, validated and packed on the host: None -> None, else a dict of CPU tensors at the caller's [B, L]:
+    params fp32 [8] (pf_sampler_temper_args.params) and tau fp32 [B, L], or None when seq_temperature is absent or the scalar 1.0.
+    ValueError with the offending value: a temperature that is not a finite number > 0, a negative or non-finite sigma, a power
+    outside {0, 1, 2}, t_off outside (0, 1], an unknown entry."""
+    if temper is None:
+        return None
+    if not isinstance(temper, dict):
+        raise ValueError(f"temper: expected None or a dict, got {type(temper).__name__}")
+    for k in temper:
+        if k not in TEMPER_DEFAULTS:
+            raise ValueError(f"temper: unknown entry {k!r}; the entries are {tuple(TEMPER_DEFAULTS)}")
+    t = {**TEMPER_DEFAULTS, **temper}
+    if t["power"] not in (0, 1, 2) or isinstance(t["power"], bool):
+        raise ValueError(f"temper['power'] = {t['power']!r}: expected 0, 1 or 2")
+    for k in ("sigma_trans", "sigma_rot", "t_off"):
+        if isinstance(t[k], bool) or not isinstance(t[k], numbers.Real):
+            raise ValueError(f"temper[{k!r}] = {t[k]!r}: expected a number")
+    vals = {k: float(t[k]) for k in _TEMPER_SLOTS}
+    for k in ("sigma_trans", "sigma_rot"):
+        if not (math.isfinite(vals[k]) and vals[k] >= 0):
+            raise ValueError(f"temper[{k!r}] = {t[k]!r}: expected a finite number >= 0")
+    if not 0.0 < vals["t_off"] <= 1.0:
+        raise ValueError(f"temper['t_off'] = {t['t_off']!r}: expected 0 < t_off <= 1")
+    params = np.zeros(_capi.TEMPER_NPARAMS, dtype=np.float32)
+    params[:len(_TEMPER_SLOTS)] = [vals[k] for k in _TEMPER_SLOTS]
+    tau, st = None, t["seq_temperature"]
+    if torch.is_tensor(st):
+        if not st.dtype.is_floating_point or tuple(st.shape) not in ((L,), (B, L)):
+            raise ValueError(f"temper['seq_temperature']: expected a number or a floating-point tensor [{L}] or [{B}, {L}], got {st.dtype} {tuple(st.shape)}")
+        p = np.broadcast_to(st.detach().to("cpu", torch.float32).numpy(), (B, L))
+        if not (np.isfinite(p) & (p > 0)).all():
+            b, l = np.argwhere(~(np.isfinite(p) & (p > 0)))[0]
+            raise ValueError(f"temper['seq_temperature']: sample {b}, residue {l} has temperature {p[b, l]}; a temperature is a finite number > 0")
+        tau = torch.from_numpy(np.array(p, dtype=np.float32))          # (a copy: the broadcast view is read-only)
+    else:
+        if isinstance(st, bool) or not isinstance(st, numbers.Real) or not (math.isfinite(st) and st > 0):
+            raise ValueError(f"temper['seq_temperature'] = {st!r}: a temperature is a finite number > 0")
+        if float(st) != 1.0:
+            tau = torch.full((B, L), float(st), dtype=torch.float32)
+    return {"params": torch.from_numpy(params), "tau": tau}
+
+
+def temper_has_noise(temper):
+    """whether a packed `temper` (make_temper) puts noise on the backbone state at all"""
+    return temper is not None and bool((temper["params"][:2] > 0).any())
+
+
+def fit_temper(temper, L0, Lk, idx=None):
+    """The packed tempering (make_temper) of the samples `idx` (None: all) with the residue axis of the temperature plane cut or padded
+    from L0 to Lk (temperature 1 on the padding: its logits are divided by one and never drawn from)."""
+    if temper is None:
+        return None
+    from .buckets import _fit, _rows
+    out = dict(temper)
+    if temper["tau"] is not None:
+        p = temper["tau"] if idx is None else _rows(temper["tau"], idx)
+        out["tau"] = _fit(p, L0, Lk, 1, 1.0)
+    return out
+
+
+def shard_temper(temper, lo, hi, total):
+    """sample()'s `temper` dict with its per-sample entry (seq_temperature [total, L]) cut to the shard [lo, hi)"""
+    if not isinstance(temper, dict):
+        return temper
+    out = dict(temper)
+    st = out.get("seq_temperature")
+    if torch.is_tensor(st) and st.dim() == 2 and st.shape[0] == total:
+        out["seq_temperature"] = st[lo:hi]
+    return out
+
+
+def check_gauss(noise, temper, num_steps, B, L):
+    """The pre-drawn normals of a call (noise["gauss"], [num_steps - 1, B, L, 6]) against its packed tempering: a run on supplied
+    categorical draws (noise["expo"]) with noise on the state must supply the normals too; without `expo` the kernel draws."""
+    g = None if noise is None else noise.get("gauss")
+    if g is not None and (not torch.is_tensor(g) or tuple(g.shape) != (num_steps - 1, B, L, 6)):
+        raise ValueError(f"noise['gauss']: expected a tensor {(num_steps - 1, B, L, 6)}, got {tuple(g.shape) if torch.is_tensor(g) else type(g).__name__}")
+    if temper_has_noise(temper) and noise is not None and noise.get("expo") is not None and g is None:
+        raise ValueError("noise['expo'] is supplied and temper has a non-zero sigma: supply noise['gauss'] "
+                         f"{(num_steps - 1, B, L, 6)} too (a run on supplied draws is supplied throughout)")
+
+
+class DeviceSampler:
+    """Owned by its engine (DenoiseEngine.sampler caches one per (num_steps, flags, cond, guide, temper)): trajectory buffers and the
+    captured graphs are reused by the next sample() call; set_seed() / set_grid() / set_context() / set_cond() / set_guide() /
+    set_temper() / init_state() are what a call changes."""
+
+    def __init__(self, engine, num_steps, flags=(True, True, True), first_sample=0, seed=0, cond=False, guide=False, temper=False):
         self.eng = engine
         self.lib = engine.lib
         self.N = num_steps
@@ -411,6 +503,21 @@ class DeviceSampler:
             g.guided_trans, g.energy, g.shift_max = self.guided_trans.data_ptr(), self.g_energy.data_ptr(), self.g_shift.data_ptr()
             g.error, g.B, g.L, g.sample_bb = self.g_error.data_ptr(), B, L, a.sample_bb
             a.pred_trans = self.guided_trans.data_ptr()
+        # tempered / stochastic calls (pf_sampler_temper between the guidance and the step kernel): the temperature plane, the tempered
+        # copy of the logits, the parameters and the pre-drawn normals live in buffers THIS sampler owns.  A call only rewrites their
+        # contents and says which of tau / gauss are NULL (set_temper, init_state); the step kernel reads the tempered copy when a
+        # plane is given and the engine's logits otherwise.
+        self.temper = bool(temper)
+        if self.temper:
+            self.t_tau, self.t_logits, self.t_params = e(rows), e(rows, 20), e(_capi.TEMPER_NPARAMS)
+            self.t_gauss = e(max(num_steps - 1, 1), rows, 6)
+            self._logits_ptr = a.pred_logits
+            t = self.targs = _capi.SamplerTemperArgs()
+            t.pred_logits, t.tempered_logits, t.tau = a.pred_logits, self.t_logits.data_ptr(), None
+            t.rot_t, t.trans_t, t.gen_mask, t.res_flags = a.rot_t, a.trans_t, a.gen_mask, None
+            t.ts, t.step, t.params, t.gauss = a.ts, a.step, self.t_params.data_ptr(), None
+            t.seed_dev, t.sample_ids = a.seed_dev, a.sample_ids
+            t.B, t.L, t.num_steps, t.sample_bb = B, L, num_steps, a.sample_bb
         self.graph = None
         self.graph_k = None
         self._graph_key = None
@@ -422,6 +529,8 @@ class DeviceSampler:
         s = int(seed) & (2 ** 64 - 1)
         s = s - 2 ** 64 if s >= 2 ** 63 else s                          # uint64 bit pattern in an int64 tensor
         self.args.seed, self.args.first_sample = int(seed) & (2 ** 64 - 1), int(first_sample)
+        if self.temper:                                 # (the noise kernel reads the key exactly as the step kernel does)
+            self.targs.seed, self.targs.first_sample = self.args.seed, self.args.first_sample
         self.seed_dev.copy_(torch.tensor([s, int(first_sample)], dtype=torch.int64))
         self.sample_ids.copy_(torch.arange(self.eng.B, dtype=torch.int64) + int(first_sample))
 
@@ -441,6 +550,8 @@ class DeviceSampler:
             key += (self.cargs.res_flags, self.cargs.aa_allowed)
         if self.guide:                                  # ... and whether the guidance kernel was launched with a hot-spot plane
             key += (self.gargs.hotspots,)
+        if self.temper:                                 # ... which of tau / gauss the noise kernel got (tau also decides the logits the step kernel reads)
+            key += (self.targs.tau, self.targs.gauss)
         return key
 
     def set_grid(self, grid):
@@ -487,6 +598,17 @@ class DeviceSampler:
         self.g_shift.zero_()
         self.g_error.zero_()
 
+    def set_temper(self, temper):
+        """The call's tempering (sampler.make_temper, temperature plane padded to the engine's length) into the owned buffers.  With a
+        plane the step kernel draws from the tempered copy of the logits, without one from the engine's own."""
+        assert self.temper, "a sampler built without temper=True has no tempering buffers"
+        self.t_params.copy_(temper["params"])
+        tau = temper.get("tau")
+        if tau is not None:
+            self.t_tau.copy_(tau.reshape(self.eng.rows))
+        self.targs.tau = self.t_tau.data_ptr() if tau is not None else None
+        self.args.pred_logits = self.t_logits.data_ptr() if tau is not None else self._logits_ptr
+
     def guidance(self):
         """The records of a guided run as CPU tensors: energy [num_steps, B, 5] (the terms of every step's UNGUIDED prediction, in the
         order of GUIDE_TERMS), shift_max [num_steps, B].  Raises if the kernel refused a restraint index."""
@@ -516,6 +638,13 @@ class DeviceSampler:
             self.args.expo = self.expo.data_ptr()
         else:
             self.expo, self.args.expo = None, None
+        if self.temper:                                # pre-drawn normals of the state noise, or NULL: the kernel draws (Philox)
+            g = noise.get("gauss")
+            if g is not None:
+                assert tuple(g.shape) == (self.N - 1, self.eng.B, self.eng.L, 6), g.shape
+                if self.N > 1:
+                    self.t_gauss.copy_(g.reshape(self.t_gauss.shape))
+            self.targs.gauss = self.t_gauss.data_ptr() if g is not None else None
         if self.cond:
             rc = self.lib.pf_sampler_init_cond(C.byref(self.args), C.byref(self.cargs), rot0.data_ptr(), tr0.data_ptr(), ang0.data_ptr(),
                                                sx0.data_ptr(), _capi.stream_ptr())
@@ -534,6 +663,10 @@ class DeviceSampler:
             self.gargs.res_flags = self.cargs.res_flags if self.cond else None
             rc = self.lib.pf_guidance_fwd(C.byref(self.gargs), _capi.stream_ptr())
             _capi.check(rc, "pf_guidance_fwd")
+        if self.temper:                                 # tempered logits and the noise on the state the step kernel steps from
+            self.targs.res_flags = self.cargs.res_flags if self.cond else None
+            rc = self.lib.pf_sampler_temper(C.byref(self.targs), _capi.stream_ptr())
+            _capi.check(rc, "pf_sampler_temper")
         if self.cond:
             rc = self.lib.pf_sampler_step_cond(C.byref(self.args), C.byref(self.cargs), _capi.stream_ptr())
             _capi.check(rc, "pf_sampler_step_cond")
