@@ -672,6 +672,82 @@ typedef struct {
 } pf_sampler_temper_args;
 int pf_sampler_temper(const pf_sampler_temper_args* a, pf_stream_t stream);
 
+/* ---- steered sampling: on-device particle resampling by guidance energy (csrc/steer.hip) --------------------------------
+ * The reference has NO such call.  Feynman-Kac steering (Singhal et al. 2025): sequential Monte Carlo over the samples of one complex
+ * (a particle GROUP) with a difference potential on the predicted clean sample and adaptive systematic resampling (Kitagawa 1996;
+ * Douc & Cappe 2005).  Written from the publications, not checked against any other program.  Off-label like the guidance and the
+ * tempering: nothing was tuned on a trained checkpoint.
+ * Two launches, called once per step AFTER pf_sampler_step*: that kernel has bumped the counter, so s = step[0] - 1; both kernels return
+ * without writing when s < 0 or s >= num_steps.  B workgroups are launched; workgroup g >= n_groups[0] returns.  Group g has the members
+ * m_0 < ... < m_{n-1} = members[group_ptr[g] .. group_ptr[g+1]), n <= PF_STEER_MAX_GROUP.  The structure lives in device memory, so the
+ * caller states its largest group in max_group: above PF_STEER_MAX_GROUP -> PF_E_TOOLARGE; a kernel that meets a group outside these
+ * limits or a member outside [0, B) leaves that group alone (its slots keep the ancestors the caller initialised: the identity).
+ * DECIDE, one workgroup of 256 threads per group, double arithmetic, every sum on one thread in ascending member order, no atomics (two
+ * runs give the same bits).  params (device double [PF_STEER_NPARAMS]): lam every ess_frac t_on t_off 0 0 0, read at run time.
+ *   E_b = (double)e[s,b,0] + e[s,b,1] + e[s,b,2] + e[s,b,3] + e[s,b,4], summed in that order from the fp32 terms pf_guidance_fwd wrote
+ *   for step s (the weighted terms of the UNGUIDED prediction).
+ *   The step is ACTIVE when t_on <= (double)ts[s] <= t_off.  Active: logw_b += -lam * (E_b - eprev_b), then eprev_b = E_b (eprev starts
+ *   at 0, so the product of the potentials telescopes to exp(-lam E) of the last active step); a non-finite E_b sets logw_b = -inf and
+ *   leaves eprev_b; a NaN log-weight counts as -inf.  Inactive: nothing changes.
+ *   A resampling MOMENT is an active step with s < num_steps - 1 and (s + 1) % every == 0.  M = max logw; M not finite at a moment ->
+ *   code -1, nothing changes.  w_i = exp(logw_i - M), S = sum w_i, Q = sum w_i^2, ESS = S^2 / Q (recorded on every step with a finite
+ *   M, else 0).  At a moment the group is resampled iff ess_frac >= 1 or ESS <= ess_frac * n (ess_frac = 0 never does).
+ *   Systematic resampling with ONE uniform u per (step, group): p_k = (u + k) / n, a_k = the first i whose raw running sum
+ *   C_i > p_k * S (rounding left none: the last i with w_i > 0), c_i = #{k : a_k = i}.  Stable assignment: a slot with c_i >= 1 keeps
+ *   its own particle; the dead slots in ascending order receive the list "i repeated c_i - 1 times, i ascending".  Then logw = 0 for the
+ *   whole group and eprev of a dead slot becomes its ancestor's.  Sources are surviving slots, destinations dead ones: disjoint sets.
+ *   Records of step s: ancestors int32 [num_steps,B] (local sample index; identity when nothing moved), logw_rec double [num_steps,B]
+ *   (after the update, before the reset), ess double [num_steps,B] and code int32 [num_steps,B] indexed by GROUP: 0 no moment, 1 a
+ *   moment with ESS above the threshold, 2 resampled, -1 degenerate.
+ * GATHER, one thread per row of B*L, only when all seven state pointers are given and s < num_steps - 1: a slot b with
+ * ancestors[s,b] != b copies row (ancestors[s,b], l) -> (b, l) of rot_t, trans_t, ang_t, seq_t, simplex_t, trans0, simplex0 as raw bits,
+ * in place (the disjointness above).
+ * u: a caller-supplied double [num_steps,B] indexed by (step, group), or NULL -> Philox4x32-10 with the sampler's key (seed / seed_dev
+ * exactly as pf_sampler_args), counter {0, 0xC0000000 | s, lo32(gs0), hi32(gs0)}, gs0 the global sample id of the group's first member
+ * (sample_ids[m_0], else first_sample + m_0), u = ((c0 >> 8) + 0.5) * 2^-24.  The categorical draws use counter[1] < 2*num_steps + 1
+ * and the temper normals 0x80000000 | s: the two high bits keep the three streams apart.
+ * STAND-ALONE (step == NULL): one decision with s = 0 that is always active and always a moment; energy [B,5], logw [B] (in / out),
+ * eprev optional (NULL: 0), u [G] or NULL, ancestors [B], ess [G], code [G]; logw_rec [B] optional; ts unused.
+ * PF_E_BADARG: a NULL struct, params, group_ptr, members, n_groups or energy; B, L, num_steps or max_group <= 0; logw, ancestors, ess or
+ * code missing; in sampler mode ts, eprev or logw_rec missing; state pointers only partly given. */
+#define PF_STEER_NPARAMS 8
+#define PF_STEER_MAX_GROUP 1024
+typedef struct {
+    /* energies and time */
+    const float* energy;           /* [num_steps,B,5] pf_guidance_args.energy (stand-alone: [B,5]) */
+    const float* ts;               /* time grid [num_steps] */
+    const int* step;               /* device step counter (pf_sampler_args.step); NULL = stand-alone */
+    const double* params;          /* device [PF_STEER_NPARAMS] */
+    /* groups */
+    const int* group_ptr;          /* device [B+1] */
+    const int* members;            /* device [B] sample indices, ascending inside a group */
+    const int* n_groups;           /* device [1] */
+    /* weights */
+    double* logw;                  /* [B] */
+    double* eprev;                 /* [B] */
+    /* uniforms */
+    const double* u;               /* optional [num_steps,B]; NULL = in-kernel Philox */
+    const uint64_t* seed_dev;      /* optional, as pf_sampler_args.seed_dev */
+    const int64_t* sample_ids;     /* optional [B], as pf_sampler_args.sample_ids */
+    /* records */
+    int* ancestors;                /* [num_steps,B] */
+    double* logw_rec;              /* [num_steps,B] */
+    double* ess;                   /* [num_steps,B] by group */
+    int* code;                     /* [num_steps,B] by group */
+    /* per-particle state of the step kernel: all seven or none */
+    float* rot_t;                  /* [B*L,9] */
+    float* trans_t;                /* [B*L,3] */
+    float* ang_t;                  /* [B*L,5] */
+    int64_t* seq_t;                /* [B*L] */
+    float* simplex_t;              /* [B*L,20] */
+    float* trans0;                 /* [B*L,3] */
+    float* simplex0;               /* [B*L,20] */
+    uint64_t seed;
+    int64_t first_sample;
+    int B, L, num_steps, max_group;
+} pf_sampler_steer_args;
+int pf_sampler_steer(const pf_sampler_steer_args* a, pf_stream_t stream);
+
 /* stand-alone manifold steps (KAT surface): so3_utils.geodesic_t (500-520) and torus.tor_geodesic_t */
 int pf_so3_geodesic(const float* base, const float* target, const float* t, float* out, int n, pf_stream_t stream);
 int pf_so3_log(const float* rot, float* rotvec, int n, pf_stream_t stream);

@@ -20,6 +20,8 @@ _i = C.c_int
 GUIDE_MAX_PAIRS, GUIDE_MAX_L, GUIDE_NPARAMS, GUIDE_NTERMS = 64, 1024, 16, 5
 # include/pepflow_hip.h, tempered and stochastic sampling
 TEMPER_NPARAMS = 8
+# include/pepflow_hip.h, steered sampling
+STEER_NPARAMS, STEER_MAX_GROUP = 8, 1024
 
 
 class LinearArgs(C.Structure):
@@ -100,6 +102,14 @@ class SamplerTemperArgs(C.Structure):
     _fields_ = [("pred_logits", _fp), ("tempered_logits", _fp), ("tau", _fp), ("rot_t", _fp), ("trans_t", _fp), ("gen_mask", _fp),
                 ("res_flags", _fp), ("ts", _fp), ("step", _fp), ("params", _fp), ("gauss", _fp), ("seed_dev", _fp), ("sample_ids", _fp),
                 ("seed", C.c_uint64), ("first_sample", C.c_int64), ("B", _i), ("L", _i), ("num_steps", _i), ("sample_bb", _i)]
+
+
+class SamplerSteerArgs(C.Structure):
+    _fields_ = [("energy", _fp), ("ts", _fp), ("step", _fp), ("params", _fp), ("group_ptr", _fp), ("members", _fp), ("n_groups", _fp),
+                ("logw", _fp), ("eprev", _fp), ("u", _fp), ("seed_dev", _fp), ("sample_ids", _fp),
+                ("ancestors", _fp), ("logw_rec", _fp), ("ess", _fp), ("code", _fp),
+                ("rot_t", _fp), ("trans_t", _fp), ("ang_t", _fp), ("seq_t", _fp), ("simplex_t", _fp), ("trans0", _fp), ("simplex0", _fp),
+                ("seed", C.c_uint64), ("first_sample", C.c_int64), ("B", _i), ("L", _i), ("num_steps", _i), ("max_group", _i)]
 
 
 class TrainArgs(C.Structure):
@@ -354,6 +364,7 @@ _SIGNATURES = {
     "pf_sampler_step_cond": ([C.POINTER(SamplerArgs), C.POINTER(SamplerCondArgs), _fp], _i),
     "pf_guidance_fwd": ([C.POINTER(GuidanceArgs), _fp], _i),
     "pf_sampler_temper": ([C.POINTER(SamplerTemperArgs), _fp], _i),
+    "pf_sampler_steer": ([C.POINTER(SamplerSteerArgs), _fp], _i),
     "pf_train_corrupt_fwd": ([C.POINTER(TrainArgs), _fp], _i),
     "pf_train_losses_fwd": ([C.POINTER(TrainArgs), _fp], _i),
     "pf_train_losses_bwd": ([C.POINTER(TrainArgs), C.POINTER(TrainBwdArgs), _fp], _i),

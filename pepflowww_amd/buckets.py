@@ -90,6 +90,8 @@ def sub_noise(noise, idx, L0, Lk):
     for k, v in noise.items():
         if v is None:
             out[k] = None
+        elif k == "resample_u":                            # [N, G] by GROUP: BucketedSampler.bind picks the bucket's columns
+            out[k] = v
         elif k in ("expo", "gauss"):                       # [2N, B, L0, 20] / [N-1, B, L0, 6]: the sample on axis 1
             w = _rows(v, idx, axis=1)
             if Lk < L0:
@@ -122,6 +124,12 @@ def sub_temper(temper, idx, L0, Lk):
     return fit_temper(temper, L0, Lk, idx)
 
 
+def sub_steer(steer, idx, L0, Lk):
+    """The packed steering (sampler.make_steer) of the samples `idx`: their groups renumbered, the caller's numbers kept in "group_ids"."""
+    from .sampler import fit_steer
+    return fit_steer(steer, L0, Lk, idx)
+
+
 def sub_cond(cond, idx, L0, Lk):
     """The packed conditioning (sampler.make_cond) of the samples `idx`, residue axis cut / padded to Lk by inert rows, like the noise."""
     from .sampler import fit_cond
@@ -146,13 +154,15 @@ class BucketedSampler:
         self._pad_rows = None
 
     # ---- set-up of one call ----------------------------------------------------------------------------------------------
-    def bind(self, batch, noise, L0, seed, first_sample, stamp=lambda name: None, grid=None, cond=None, guide=None, temper=None):
+    def bind(self, batch, noise, L0, seed, first_sample, stamp=lambda name: None, grid=None, cond=None, guide=None, temper=None, steer=None):
         """batch / noise: the caller's ([B, L0, ...], not padded).  Builds (or fetches from the encoder's cache) one engine + sampler
         per bucket, encodes each sub-batch into its engine's pair buffer and initialises the sampler states.  grid / cond: the call's
         time grid (None: the reference's) and packed conditioning (sampler.make_cond), sliced and padded per bucket like the noise;
         they stay in the samplers' own buffers, so the re-initialisation after the calibration probes is the conditioned one too.
         guide: the call's packed guidance (sampler.make_guide), sliced per bucket the same way.
-        temper: the call's packed tempering (sampler.make_temper), likewise; the pre-drawn normals follow the samples with the noise."""
+        temper: the call's packed tempering (sampler.make_temper), likewise; the pre-drawn normals follow the samples with the noise.
+        steer: the call's packed steering (sampler.make_steer): a bucket gets its own groups (members share a length, so no bucket cuts
+        a group) and the columns of noise["resample_u"] that belong to them."""
         if grid is None:
             from .sampler import make_grid
             grid = make_grid(self.N)
@@ -174,7 +184,7 @@ class BucketedSampler:
             stamp("encode")
             eng.bind_context(node, edge, sb["res_mask"])
             stamp("bind")
-            smp = eng.sampler(self.N, self.flags, cond=cond is not None, guide=guide is not None, temper=temper is not None)
+            smp = eng.sampler(self.N, self.flags, cond=cond is not None, guide=guide is not None, temper=temper is not None, steer=steer is not None)
             smp.set_seed(seed, first_sample)
             smp.set_grid(grid)
             ids = torch.as_tensor(idx, dtype=torch.int64) + int(first_sample)
@@ -186,6 +196,11 @@ class BucketedSampler:
                 smp.set_guide(sub_guide(guide, idx, L0, Lk))
             if temper is not None:
                 smp.set_temper(sub_temper(temper, idx, L0, Lk))
+            if steer is not None:
+                st = sub_steer(steer, idx, L0, Lk)
+                smp.set_steer(st)
+                if nz.get("resample_u") is not None:
+                    nz["resample_u"] = nz["resample_u"][:, st["group_ids"]].contiguous()
             smp.init_state(nz)
             self._nz.append(nz)
             smp.L_out = Lk
@@ -330,6 +345,23 @@ class BucketedSampler:
         for rec, (idx, _) in zip(recs, self.plan):
             energy[:, idx], shift[:, idx] = rec["energy"], rec["shift_max"]
         return {"energy": energy, "shift_max": shift, "terms": recs[0]["terms"]}
+
+    def steering(self):
+        """The buckets' steering records in the caller's sample order and group numbering (DeviceSampler.steering)."""
+        recs = [s.steering() for s in self.samplers]
+        B, N = self.eng.B, self.N
+        G = sum(r["ess"].shape[1] for r in recs)
+        out = {"ancestors": torch.zeros(N, B, dtype=torch.int64), "logw": torch.zeros(N, B, dtype=torch.float64),
+               "ess": torch.zeros(N, G, dtype=torch.float64), "code": torch.zeros(N, G, dtype=torch.int32),
+               "groups": torch.zeros(B, dtype=torch.int64), "weights": torch.zeros(B, dtype=torch.float64),
+               "group_ids": torch.arange(G, dtype=torch.int64)}
+        for rec, (idx, _) in zip(recs, self.plan):
+            ix = torch.as_tensor(idx, dtype=torch.int64)
+            out["ancestors"][:, ix] = ix[rec["ancestors"]]
+            out["logw"][:, ix], out["weights"][ix] = rec["logw"], rec["weights"]
+            out["groups"][ix] = rec["group_ids"][rec["groups"]]
+            out["ess"][:, rec["group_ids"]], out["code"][:, rec["group_ids"]] = rec["ess"], rec["code"]
+        return out
 
     def operand_range(self):
         reps = [e.operand_range() for e in self.engines]

@@ -48,7 +48,7 @@ def shard_batch(batch, world, rank):
 
 def shard_noise(noise, lo, hi):
     """the pre-drawn noise of the samples [lo, hi): expo [2N, B, L, 20] and gauss [N-1, B, L, 6] carry the sample on axis 1"""
-    return {k: (v[:, lo:hi] if k in ("expo", "gauss") else v[lo:hi]).contiguous() for k, v in noise.items() if v is not None}
+    return {k: (v[:, lo:hi] if k in ("expo", "gauss") else v if k == "resample_u" else v[lo:hi]).contiguous() for k, v in noise.items() if v is not None}
 
 
 def pack_state(step_dict):
@@ -176,13 +176,20 @@ def sample_sharded(model, batch, num_steps=100, *, noise=None, seed=None, group=
     nz = shard_noise(noise, lo, hi) if noise is not None else seeded_noise(lo, hi, L, seed)
     sizes = [shard_bounds(total, world, r)[1] - shard_bounds(total, world, r)[0] for r in range(world)]
     if hi > lo:
-        from .sampler import shard_cond_kwargs, shard_guide, shard_temper
+        from .sampler import shard_cond_kwargs, shard_guide, shard_steer, shard_temper, steer_groups_of_shard
         kw = shard_cond_kwargs(kw, lo, hi, total)      # per-sample conditioning (row flags, allowed classes, start state): this shard's rows
         if kw.get("guide") is not None:
             kw["guide"] = shard_guide(kw["guide"], lo, hi, total)      # ... and this shard's hot spots and restraint lists
         if kw.get("temper") is not None:
             kw["temper"] = shard_temper(kw["temper"], lo, hi, total)    # ... and its temperature plane
+        if kw.get("steer") is not None:                                # ... and its particle groups: whole ones only (ValueError otherwise)
+            if nz.get("resample_u") is not None:                       # [N, G] by group: the columns of this shard's groups
+                nz["resample_u"] = nz["resample_u"][:, steer_groups_of_shard(kw["steer"], lo, hi, total)].contiguous()
+            kw["steer"] = shard_steer(kw["steer"], lo, hi, total)
         smp = model.sample(local, num_steps, noise=nz, seed=seed, first_sample=lo, return_sampler=True, **kw)
+        if getattr(model, "last_steering", None) is not None:          # this rank's own records, sample indices made global
+            model.last_steering["ancestors"] += lo
+            model.last_steering["first_sample"] = lo
         packed = _final_state_of(smp)
     else:
         packed = torch.zeros(0, L, PACK_WIDTH, dtype=torch.float32, device=batch["aa"].device)

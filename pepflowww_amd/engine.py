@@ -753,24 +753,25 @@ class DenoiseEngine:
 
     SAMPLER_CACHE = 2
 
-    def sampler(self, num_steps, flags=(True, True, True), cond=False, guide=False, temper=False):
+    def sampler(self, num_steps, flags=(True, True, True), cond=False, guide=False, temper=False, steer=False):
         """DeviceSampler of this engine for (num_steps, flags, cond, guide, temper), cached with its trajectory buffers and captured graphs (the
         Philox seed and the shard offset are read from device memory, so the same graph serves every call).  cond: a sampler of the
         conditioned entry points (partial start / per-residue constraints) -- a different launch, so a different sampler.  guide: a
         sampler that launches pf_guidance_fwd in front of the step kernel (guided sampling) -- one more launch, so a different sampler.
-        temper: a sampler that launches pf_sampler_temper in front of the step kernel (tempered / stochastic sampling) -- likewise."""
+        temper: a sampler that launches pf_sampler_temper in front of the step kernel (tempered / stochastic sampling) -- likewise.
+        steer: a sampler that launches pf_sampler_steer behind the step kernel (steered sampling) -- two more launches, likewise."""
         from .sampler import DeviceSampler
-        key = (int(num_steps), tuple(bool(f) for f in flags)) + ((True,) if cond else ()) + (("guide",) if guide else ()) + (("temper",) if temper else ())
+        key = (int(num_steps), tuple(bool(f) for f in flags)) + ((True,) if cond else ()) + (("guide",) if guide else ()) + (("temper",) if temper else ()) + (("steer",) if steer else ())
         smp = self._samplers.get(key)
         if smp is None:
             try:
-                smp = DeviceSampler(self, num_steps, flags, cond=cond, guide=guide, temper=temper)
+                smp = DeviceSampler(self, num_steps, flags, cond=cond, guide=guide, temper=temper, steer=steer)
             except torch.cuda.OutOfMemoryError:                 # trajectory buffers: drop the other samplers / engines, one retry
                 self._samplers.clear()
                 if self._owner is not None:
                     self._owner._make_room(self)
                 torch.cuda.empty_cache()
-                smp = DeviceSampler(self, num_steps, flags, cond=cond, guide=guide, temper=temper)
+                smp = DeviceSampler(self, num_steps, flags, cond=cond, guide=guide, temper=temper, steer=steer)
             self._samplers[key] = smp
             while len(self._samplers) > self.SAMPLER_CACHE:
                 self._samplers.popitem(last=False)

@@ -10,7 +10,8 @@ from torch import nn
 
 from . import _capi, featurize
 from .modules import EdgeEmbedder, GAEncoder, NodeEmbedder
-from .sampler import DeviceSampler, check_gauss, default_noise, fit_cond, fit_guide, fit_temper, make_cond, make_guide, make_temper
+from .sampler import (DeviceSampler, check_gauss, check_resample_u, default_noise, fit_cond, fit_guide, fit_temper, make_cond, make_guide,
+                      make_steer, make_temper)
 from .train_forward import TrainForward, default_train_noise
 
 MAX_NUM_HEAVYATOMS = 15     # pepflow/modules/protein/constants.py:91
@@ -45,6 +46,8 @@ def _pad_residues(batch, noise, L0, L):
     for k, v in noise.items():
         if v is None:
             nz[k] = None
+        elif k == "resample_u":                          # [N, G]: one uniform per (step, group), no residue axis
+            nz[k] = v
         elif k in ("expo", "gauss"):                     # [2N, B, L0, 20] / [N-1, B, L0, 6]; padded draws are never used (1.0 keeps p / E finite)
             nz[k] = _pad_axis1(v.reshape((-1, L0) + tuple(v.shape[3:])), L - L0, 1.0 if k == "expo" else 0.0).reshape(tuple(v.shape[:2]) + (L,) + tuple(v.shape[3:]))
         elif k == "rot0":                                # [B, L0, 3, 3]: identity frames on the padding
@@ -158,7 +161,8 @@ class FlowModel(nn.Module):
 
     def _sample_impl(self, batch, num_steps=100, sample_bb=True, sample_ang=True, sample_seq=True, *,
                noise=None, seed=None, first_sample=0, use_graph=True, return_sampler=False, timings=None, pageable=False, check_range=True,
-               buckets="auto", gc_collect=True, calibrate=True, t_start=None, ts=None, start=None, aa_allowed=None, guide=None, temper=None, _gc_was_enabled=None):
+               buckets="auto", gc_collect=True, calibrate=True, t_start=None, ts=None, start=None, aa_allowed=None, guide=None, temper=None, steer=None,
+               _gc_was_enabled=None):
         """Reference signature + keyword-only extensions:
         t_start      the time grid becomes linspace(t_start, 1, num_steps) instead of linspace(1e-2, 1, num_steps); 0 < t_start < 1;
         ts           an explicit grid: num_steps strictly increasing values in (0, 1] (excludes t_start);
@@ -187,8 +191,19 @@ class FlowModel(nn.Module):
                      tangent-space Gaussian) the rotation state of the generated residues whose backbone is sampled, on every step
                      but the last; power=1 (0, 1 or 2), t_off=1.0 (no noise from that time on).  The reference has no such call: an
                      OFF-LABEL use of the trained flow, and the defaults are starting values, not tuned ones;
-        noise        dict(rot0, trans0, ang0, simplex0[, expo][, gauss]) of pre-drawn noise (parity tests); gauss [num_steps-1,B,L,6]:
-                     the normals of the state noise -- required beside expo when temper has a non-zero sigma (else drawn on the device);
+        steer        None, or a dict that switches STEERED sampling on (csrc/steer.hip; formulas: INTEGRATION.md): the samples of one
+                     complex are the particles of a group; after every step their log-weights take -lam * (E - E_prev) of the
+                     guidance energies (needs `guide`; guide["scale"] = 0 steers without a gradient shift), and at every `every`-th
+                     step a group whose effective sample size is at most ess_frac * n is resampled systematically on the device:
+                     dead slots continue from copies of surviving ones, which diverge through later noise (temper sigmas, sequence
+                     draws).  Entries: groups=None (one group: the whole batch; or an integer tensor [B] of labels; the members of a
+                     group must be exchangeable, i.e. equal inputs, and at most 1024), lam=1.0, every=1, ess_frac=0.5, t_on=0.0,
+                     t_off=1.0.  Afterwards `model.last_steering` = {"ancestors", "logw" [num_steps,B], "ess", "code" [num_steps,G],
+                     "groups", "weights" [B]} (CPU tensors; sampler.steer_lineage reads one particle's path).  The reference has no
+                     such call: an OFF-LABEL use of the trained flow, and the defaults are starting values, not tuned ones;
+        noise        dict(rot0, trans0, ang0, simplex0[, expo][, gauss][, resample_u]) of pre-drawn noise (parity tests); gauss
+                     [num_steps-1,B,L,6]: the normals of the state noise -- required beside expo when temper has a non-zero sigma (else
+                     drawn on the device); resample_u [num_steps,G]: the resampling uniforms of a steered call, likewise;
         seed         Philox seed for the in-kernel categorical draws (default: from torch's CPU generator); with noise=None an
                      explicit seed also keys the initial noise per GLOBAL sample index (distributed.seeded_noise);
         first_sample global index of this shard's first sample (world-size independent RNG streams);
@@ -234,6 +249,9 @@ class FlowModel(nn.Module):
         self.last_guidance = None                      # the per-step energies and largest shifts of a guided call
         temper = make_temper(temper, B, L0)
         check_gauss(noise, temper, int(num_steps), B, L0)
+        steer = make_steer(steer, B, L0, batch, cond, guide, temper)
+        check_resample_u(noise, steer, int(num_steps))
+        self.last_steering = None                      # the ancestor record, log-weights, ESS and codes of a steered call
         if noise is None:
             if seed is None:
                 noise = default_noise(B, L0)          # torch's global CPU generator, like the reference (flow_model.py:252-277)
@@ -247,7 +265,7 @@ class FlowModel(nn.Module):
             if len(plan) > 1:
                 return self._sample_bucketed(plan, batch, num_steps, flags, noise, seed, first_sample,
                                              use_graph, return_sampler, timings, pageable, check_range, stamp, gc_collect, calibrate, _gc_was_enabled,
-                                             grid=grid, cond=cond, guide=guide, temper=temper)
+                                             grid=grid, cond=cond, guide=guide, temper=temper, steer=steer)
         # Residue axis padded to a multiple of 16 internally (what PaddingCollate does to a shorter sample of a batch: pad values,
         # res_mask False -- padded residues are inert, tests/test_gpu_parity.py ragged cases): every kernel then runs its
         # full-tile path (16-row / 16-key tiles, float4 rows of the [B,8,L,L] buffers).  In-kernel random draws are keyed by
@@ -269,7 +287,7 @@ class FlowModel(nn.Module):
         stamp("bind")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        smp = eng.sampler(num_steps, flags, cond=cond is not None, guide=guide is not None, temper=temper is not None)
+        smp = eng.sampler(num_steps, flags, cond=cond is not None, guide=guide is not None, temper=temper is not None, steer=steer is not None)
         smp.set_seed(seed, first_sample)
         smp.set_grid(grid)
         smp.set_context(R1, x1, ang1, seq1, batch["generate_mask"])
@@ -279,6 +297,8 @@ class FlowModel(nn.Module):
             smp.set_guide(guide)
         if temper is not None:
             smp.set_temper(temper)
+        if steer is not None:
+            smp.set_steer(steer)
         smp.init_state(noise)
         stamp("setup")
         if use_graph and timings is not None and smp.needs_capture():
@@ -310,6 +330,8 @@ class FlowModel(nn.Module):
         smp.L_out = L0
         if guide is not None:
             self.last_guidance = smp.guidance()
+        if steer is not None:
+            self.last_steering = smp.steering()
         if return_sampler:
             return smp                                 # (owned by the engine: the next sample() call at this shape reuses it)
         traj = smp.trajectory(pageable=pageable)
@@ -318,10 +340,10 @@ class FlowModel(nn.Module):
 
     def _sample_bucketed(self, plan, batch, num_steps, flags, noise, seed, first_sample, use_graph, return_sampler, timings, pageable,
                          check_range, stamp, gc_collect=True, calibrate=True, _gc_was_enabled=None, grid=None, cond=None, guide=None,
-                         temper=None):
+                         temper=None, steer=None):
         """sample() of a ragged batch through its length buckets (pepflowww_amd/buckets.py): same inputs, noise, Philox streams and
         output format as the unsplit path.  grid / cond / guide / temper: the call's time grid, packed conditioning (sampler.make_cond),
-        packed guidance (sampler.make_guide) and packed tempering (sampler.make_temper)."""
+        packed guidance (sampler.make_guide), packed tempering (sampler.make_temper) and packed steering (sampler.make_steer)."""
         from .buckets import BucketedSampler
         stamp("noise")
         B, L0 = batch["aa"].shape
@@ -330,7 +352,7 @@ class FlowModel(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         smp = BucketedSampler(self, plan, B, L, num_steps, flags)
         smp.calibrate = bool(calibrate)
-        smp.bind(batch, noise, L0, seed, first_sample, stamp, grid=grid, cond=cond, guide=guide, temper=temper)
+        smp.bind(batch, noise, L0, seed, first_sample, stamp, grid=grid, cond=cond, guide=guide, temper=temper, steer=steer)
         if use_graph and timings is not None and smp.needs_capture():
             smp.capture()
             stamp("capture")
@@ -353,6 +375,8 @@ class FlowModel(nn.Module):
         self.last_buckets = [(len(idx), Lk) for idx, Lk in plan]
         if guide is not None:
             self.last_guidance = smp.guidance()
+        if steer is not None:
+            self.last_steering = smp.steering()
         if return_sampler:
             return smp
         traj = smp.trajectory(pageable=pageable)

@@ -1649,3 +1649,61 @@ def ca_potential(x, peptide, movable, context, hotspots=None, restraints=None, t
     if bool((err != 0).any()):
         raise _capi.PepflowHipError("pf_guidance_fwd refused a restraint index outside the sample")
     return out
+
+
+def resample_particles(logw, groups=None, u=None, ess_frac=1.0, seed=0, state=None):
+    """pf_sampler_steer in its stand-alone mode: one adaptive systematic resampling decision per particle group, as
+    `FlowModel.sample(steer=...)` takes it after a step.
+
+    logw [B] log-weights (device tensor; -inf and NaN count as weight 0); groups: None (one group) or an integer tensor [B] of arbitrary
+    labels, at most 1024 members each; u: None (Philox4x32-10 with `seed`, keyed by the group's first member) or [G] uniforms in [0, 1),
+    one per group in the order of the groups' first members; ess_frac in [0, 1]: a group is resampled iff its effective sample size is
+    at most ess_frac * n (1: always, 0: never).  state: None, or the seven per-particle tensors (rot_t [B,L,9], trans_t [B,L,3], ang_t
+    [B,L,5], seq_t int64 [B,L], simplex_t [B,L,20], trans0 [B,L,3], simplex0 [B,L,20]; contiguous device tensors) to gather IN PLACE.
+    -> dict of device tensors: ancestors int64 [B] (the sample every slot continues from; sources are surviving slots), ess float64 [G],
+    code int32 [G] (1 not resampled, 2 resampled, -1 no finite weight), logw float64 [B] (0 in a resampled group), groups int64 [B]."""
+    import numpy as np
+    from . import sampler as S
+    if not isinstance(logw, torch.Tensor) or logw.dim() != 1:
+        raise ValueError(f"logw must be a tensor [B], got {tuple(getattr(logw, 'shape', ()))}")
+    B, dev = logw.shape[0], logw.device
+    _capi.dptr(logw, logw.dtype, "logw")                       # a CPU tensor raises: no fallback
+    if isinstance(ess_frac, bool) or not 0.0 <= float(ess_frac) <= 1.0:
+        raise ValueError(f"ess_frac = {ess_frac!r}: expected a number in [0, 1]")
+    if groups is not None and (not isinstance(groups, torch.Tensor) or groups.dtype.is_floating_point or groups.dtype == torch.bool or tuple(groups.shape) != (B,)):
+        raise ValueError(f"groups: expected None or an integer tensor [{B}]")
+    if B == 0:
+        raise ValueError("logw is empty")
+    ptr, members, group_of, G = S.pack_groups(np.zeros(B, dtype=np.int64) if groups is None else groups.detach().cpu().numpy())
+    sizes = np.diff(ptr[:G + 1])
+    if sizes.max() > _capi.STEER_MAX_GROUP:
+        raise ValueError(f"group {int(sizes.argmax())} has {int(sizes.max())} members; at most {_capi.STEER_MAX_GROUP}")
+    keep = {"params": torch.tensor([0.0, 1.0, float(ess_frac), 0.0, 1.0, 0.0, 0.0, 0.0], dtype=torch.float64, device=dev),
+            "group_ptr": torch.from_numpy(ptr).to(dev), "members": torch.from_numpy(members).to(dev),
+            "n_groups": torch.tensor([G], dtype=torch.int32, device=dev), "energy": torch.zeros(B, 5, device=dev),
+            "logw": logw.detach().to(torch.float64).clone().contiguous()}
+    out = {"ancestors": torch.arange(B, dtype=torch.int32, device=dev), "ess": torch.zeros(G, dtype=torch.float64, device=dev),
+           "code": torch.zeros(G, dtype=torch.int32, device=dev)}
+    a = _capi.SamplerSteerArgs()
+    _bind_in(a, **keep, **out)
+    if u is not None:
+        uu = torch.as_tensor(u, dtype=torch.float64).reshape(-1)
+        if uu.numel() != G or not bool(((uu >= 0) & (uu < 1)).all()):
+            raise ValueError(f"u: expected {G} values in [0, 1), one per group")
+        keep["u"] = uu.to(dev).contiguous()
+        a.u = keep["u"].data_ptr()
+    L = 1
+    if state is not None:
+        names = ("rot_t", "trans_t", "ang_t", "seq_t", "simplex_t", "trans0", "simplex0")
+        if len(state) != 7:
+            raise ValueError(f"state: expected the seven tensors {names}")
+        L = state[0].shape[1]
+        for name, v, wd in zip(names, state, (9, 3, 5, 1, 20, 3, 20)):
+            want = torch.int64 if name == "seq_t" else torch.float32
+            if not isinstance(v, torch.Tensor) or v.dtype != want or v.device != dev or not v.is_contiguous() or v.numel() != B * L * wd or v.shape[0] != B:
+                raise ValueError(f"state {name}: expected a contiguous {want} tensor [{B}, {L}, {wd}] on {dev}")
+            setattr(a, name, _capi.dptr(v, want, name))
+    a.seed, a.first_sample, a.B, a.L, a.num_steps, a.max_group = int(seed) & (2 ** 64 - 1), 0, B, L, 1, int(sizes.max())
+    _capi.check(_capi.load().pf_sampler_steer(C.byref(a), _capi.stream_ptr()), "pf_sampler_steer")
+    return {"ancestors": out["ancestors"].to(torch.int64), "ess": out["ess"], "code": out["code"], "logw": keep["logw"],
+            "groups": torch.from_numpy(group_of).to(dev, torch.int64)}

@@ -434,12 +434,192 @@ def check_gauss(noise, temper, num_steps, B, L):
                          f"{(num_steps - 1, B, L, 6)} too (a run on supplied draws is supplied throughout)")
 
 
-class DeviceSampler:
-    """Owned by its engine (DenoiseEngine.sampler caches one per (num_steps, flags, cond, guide, temper)): trajectory buffers and the
-    captured graphs are reused by the next sample() call; set_seed() / set_grid() / set_context() / set_cond() / set_guide() /
-    set_temper() / init_state() are what a call changes."""
+# ---- steered sampling: host-side validation and packing (no GPU needed) ----------------------------------------------------------
+# Feynman-Kac steering: the samples of one complex are the particles of a group, weighted by a difference potential of the guidance
+# energies and resampled systematically when their effective sample size drops (csrc/steer.hip; formulas: include/pepflow_hip.h and
+# INTEGRATION.md).  The reference has none of this: like the guidance and the tempering an OFF-LABEL use of the trained flow.  The
+# defaults are starting values: nothing has been tuned on a trained checkpoint.
+STEER_DEFAULTS = {"groups": None, "lam": 1.0, "every": 1, "ess_frac": 0.5, "t_on": 0.0, "t_off": 1.0}
+_STEER_SLOTS = ("lam", "every", "ess_frac", "t_on", "t_off")       # slots of the device parameter vector (pf_sampler_steer_args.params)
 
-    def __init__(self, engine, num_steps, flags=(True, True, True), first_sample=0, seed=0, cond=False, guide=False, temper=False):
+
+def pack_groups(labels):
+    """arbitrary integer labels [B] -> (group_ptr int32 [B+1], members int32 [B], group_of int32 [B], n_groups).  Groups are numbered
+    by their first member; the members of a group ascend.  group_ptr beyond n_groups repeats B."""
+    lab = np.asarray(labels).reshape(-1)
+    B = lab.shape[0]
+    number, group_of = {}, np.zeros(B, dtype=np.int32)
+    for b in range(B):
+        group_of[b] = number.setdefault(int(lab[b]), len(number))
+    G = len(number)
+    members = np.argsort(group_of, kind="stable").astype(np.int32)
+    ptr = np.full(B + 1, B, dtype=np.int32)
+    ptr[:G + 1] = np.concatenate([[0], np.cumsum(np.bincount(group_of, minlength=G))])
+    return ptr, members, group_of, G
+
+
+def _steer_rows(batch, cond, guide, temper):
+    """(name, tensor with the sample on axis 0) of everything the members of a group must share"""
+    out = [(f"batch[{k!r}]", v) for k, v in batch.items() if torch.is_tensor(v) and v.dim() >= 1]
+    for name, packed, keys in (("cond", cond, COND_ROW_KEYS), ("guide", guide, ("hotspots", "pair_idx", "pair_par")), ("temper", temper, ("tau",))):
+        if packed is not None:
+            out += [(f"{name}[{k!r}]", packed[k]) for k in keys if packed.get(k) is not None]
+    return out
+
+
+def make_steer(steer, B, L, batch=None, cond=None, guide=None, temper=None):
+    """sample()'s `steer` dict, validated and packed on the host: None -> None, else a dict: params float64 [8]
+    (pf_sampler_steer_args.params), group_ptr int32 [B+1], members int32 [B] (ascending inside a group), group_of int32 [B], n_groups,
+    max_group.  batch / cond / guide / temper: the call's batch and its packed conditioning, guidance and tempering; the members of a
+    group must be EXCHANGEABLE: every batch tensor and every per-sample entry of the three equal across them (what
+    design.make_design_batch(n_samples=...) produces).  ValueError with the offending value: an unknown entry, steer without guide (the
+    energies are the guidance's; guide["scale"] = 0 steers without a gradient shift), lam not a finite number >= 0, every not an
+    integer >= 1, ess_frac outside [0, 1], not 0 <= t_on <= t_off <= 1, groups not an integer tensor [B], a group of more than 1024
+    members, members that differ (the first differing key and the sample pair are named)."""
+    if steer is None:
+        return None
+    if not isinstance(steer, dict):
+        raise ValueError(f"steer: expected None or a dict, got {type(steer).__name__}")
+    for k in steer:
+        if k not in STEER_DEFAULTS:
+            raise ValueError(f"steer: unknown entry {k!r}; the entries are {tuple(STEER_DEFAULTS)}")
+    if guide is None:
+        raise ValueError("steer needs guide: the energies the particles are weighted by are the guidance's (guide['scale'] = 0 steers "
+                         "without a gradient shift)")
+    s = {**STEER_DEFAULTS, **steer}
+    for k in _STEER_SLOTS:
+        if isinstance(s[k], bool) or not isinstance(s[k], numbers.Real):
+            raise ValueError(f"steer[{k!r}] = {s[k]!r}: expected a number")
+    if not (math.isfinite(s["lam"]) and s["lam"] >= 0):
+        raise ValueError(f"steer['lam'] = {s['lam']!r}: expected a finite number >= 0")
+    if not isinstance(s["every"], numbers.Integral) or s["every"] < 1:
+        raise ValueError(f"steer['every'] = {s['every']!r}: expected an integer >= 1")
+    if not 0.0 <= s["ess_frac"] <= 1.0:
+        raise ValueError(f"steer['ess_frac'] = {s['ess_frac']!r}: expected a number in [0, 1]")
+    if not 0.0 <= s["t_on"] <= s["t_off"] <= 1.0:
+        raise ValueError(f"steer['t_on'] = {s['t_on']!r}, steer['t_off'] = {s['t_off']!r}: expected 0 <= t_on <= t_off <= 1")
+    gr = s["groups"]
+    if gr is None:
+        labels = np.zeros(B, dtype=np.int64)
+    else:
+        if not torch.is_tensor(gr) or gr.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or tuple(gr.shape) != (B,):
+            raise ValueError(f"steer['groups']: expected None or an integer tensor [{B}], got "
+                             f"{(str(gr.dtype) + ' ' + str(tuple(gr.shape))) if torch.is_tensor(gr) else type(gr).__name__}")
+        labels = gr.detach().cpu().numpy().astype(np.int64)
+    ptr, members, group_of, G = pack_groups(labels)
+    sizes = np.diff(ptr[:G + 1])
+    if sizes.max() > _capi.STEER_MAX_GROUP:
+        g = int(sizes.argmax())
+        raise ValueError(f"steer['groups']: group {int(labels[members[ptr[g]]])} has {int(sizes[g])} members; at most {_capi.STEER_MAX_GROUP}")
+    rows = _steer_rows(batch or {}, cond, guide, temper)
+    for g in range(G):
+        m = members[ptr[g]:ptr[g + 1]]
+        if len(m) < 2:
+            continue
+        for name, v in rows:
+            if v.shape[0] != B:
+                continue
+            w = v.detach()[torch.as_tensor(m, dtype=torch.int64, device=v.device)]
+            same = (w == w[:1]) | ((w != w) & (w[:1] != w[:1])) if w.dtype.is_floating_point else w == w[:1]
+            if not bool(same.all()):
+                j = int((~same.reshape(len(m), -1).all(1)).nonzero()[0])
+                raise ValueError(f"steer: the members of a group must be exchangeable, but {name} differs between samples {int(m[0])} and "
+                                 f"{int(m[j])} of group {int(labels[m[0]])}")
+    params = np.zeros(_capi.STEER_NPARAMS, dtype=np.float64)
+    params[:len(_STEER_SLOTS)] = [float(s[k]) for k in _STEER_SLOTS]
+    return {"params": torch.from_numpy(params), "group_ptr": torch.from_numpy(ptr), "members": torch.from_numpy(members),
+            "group_of": torch.from_numpy(group_of), "n_groups": G, "max_group": int(sizes.max()),
+            "group_ids": torch.arange(G, dtype=torch.int64)}
+
+
+def fit_steer(steer, L0, Lk, idx=None):
+    """The packed steering (make_steer) of the samples `idx` (None: all): their groups renumbered, "group_ids" = the caller's number of
+    every group kept (the columns of noise["resample_u"] and of the records).  Nothing of it lies on the residue axis.  A group that
+    `idx` cuts raises ValueError (length buckets cannot cut one: its members share a length)."""
+    if steer is None or idx is None:
+        return steer
+    idx = np.asarray(idx, dtype=np.int64)
+    of = steer["group_of"].numpy()
+    sub = of[idx]
+    whole = np.bincount(of, minlength=steer["n_groups"])
+    part = np.bincount(sub, minlength=steer["n_groups"])
+    cut = np.nonzero((part > 0) & (part != whole))[0]
+    if len(cut):
+        raise ValueError(f"steer: group {int(cut[0])} is cut: {int(part[cut[0]])} of its {int(whole[cut[0]])} members are in this part of the batch")
+    ptr, members, group_of, G = pack_groups(sub)
+    ids = steer["group_ids"].numpy()[sub[members[ptr[:G]]]]
+    return {**steer, "group_ptr": torch.from_numpy(ptr), "members": torch.from_numpy(members), "group_of": torch.from_numpy(group_of),
+            "n_groups": G, "max_group": int(np.diff(ptr[:G + 1]).max()), "group_ids": torch.from_numpy(np.ascontiguousarray(ids))}
+
+
+def shard_steer(steer, lo, hi, total):
+    """sample()'s `steer` dict with its per-sample entry (groups [total]) cut to the shard [lo, hi).  A boundary that cuts a group
+    raises ValueError naming the group: particles are not resampled across ranks."""
+    if not isinstance(steer, dict):
+        return steer
+    out = dict(steer)
+    gr = out.get("groups")
+    lab = np.zeros(total, dtype=np.int64) if gr is None else torch.as_tensor(gr).detach().cpu().numpy().reshape(-1)
+    if lab.shape[0] != total:
+        return out
+    inside = set(lab[lo:hi].tolist())
+    outside = set(lab[:lo].tolist()) | set(lab[hi:].tolist())
+    cut = sorted(inside & outside)
+    if cut:
+        raise ValueError(f"steer: the shard [{lo}, {hi}) cuts group {cut[0]}; a group must lie on one rank")
+    if gr is not None:
+        out["groups"] = torch.as_tensor(gr)[lo:hi]
+    return out
+
+
+def steer_groups_of_shard(steer, lo, hi, total):
+    """the caller's group numbers (columns of noise["resample_u"]) of the groups in the shard [lo, hi): groups are numbered by their
+    first member, so a shard of whole groups holds a consecutive run of them"""
+    gr = None if not isinstance(steer, dict) else steer.get("groups")
+    lab = np.zeros(total, dtype=np.int64) if gr is None else torch.as_tensor(gr).detach().cpu().numpy().reshape(-1)
+    of = pack_groups(lab)[2]
+    return sorted(set(of[lo:hi].tolist()))
+
+
+def steer_lineage(ancestors):
+    """ancestors [num_steps, B] (the record of a steered run) -> int64 [num_steps, B]: for every FINAL slot b the slot its particle
+    sat in at each step, lineage[num_steps-1, b] = b and lineage[s, b] = ancestors[s, lineage[s+1, b]].  Reading step s of the
+    slot-indexed trajectory at lineage[s, b] gives one particle's coherent path.  Pure host code."""
+    a = torch.as_tensor(ancestors).detach().cpu().to(torch.int64)
+    N, B = a.shape
+    lin = torch.empty(N, B, dtype=torch.int64)
+    lin[N - 1] = torch.arange(B)
+    for s in range(N - 2, -1, -1):
+        lin[s] = a[s][lin[s + 1]]
+    return lin
+
+
+def check_resample_u(noise, steer, num_steps):
+    """The pre-drawn uniforms of a call (noise["resample_u"], [num_steps, G], values in [0, 1)) against its packed steering: a run on
+    supplied categorical draws (noise["expo"]) must supply them too, the rule of `gauss`; without `expo` the kernel draws."""
+    u = None if noise is None else noise.get("resample_u")
+    if u is not None and steer is None:
+        raise ValueError("noise['resample_u'] is given but the call is not steered")
+    if steer is None:
+        return
+    G = steer["n_groups"]
+    if u is not None:
+        if not torch.is_tensor(u) or tuple(u.shape) != (num_steps, G):
+            raise ValueError(f"noise['resample_u']: expected a tensor {(num_steps, G)}, got {tuple(u.shape) if torch.is_tensor(u) else type(u).__name__}")
+        if not bool(((u >= 0) & (u < 1)).all()):
+            raise ValueError("noise['resample_u']: expected values in [0, 1)")
+    elif noise is not None and noise.get("expo") is not None:
+        raise ValueError(f"noise['expo'] is supplied and the call is steered: supply noise['resample_u'] {(num_steps, G)} too "
+                         "(a run on supplied draws is supplied throughout)")
+
+
+class DeviceSampler:
+    """Owned by its engine (DenoiseEngine.sampler caches one per (num_steps, flags, cond, guide, temper, steer)): trajectory buffers and
+    the captured graphs are reused by the next sample() call; set_seed() / set_grid() / set_context() / set_cond() / set_guide() /
+    set_temper() / set_steer() / init_state() are what a call changes."""
+
+    def __init__(self, engine, num_steps, flags=(True, True, True), first_sample=0, seed=0, cond=False, guide=False, temper=False,
+                 steer=False):
         self.eng = engine
         self.lib = engine.lib
         self.N = num_steps
@@ -518,6 +698,28 @@ class DeviceSampler:
             t.ts, t.step, t.params, t.gauss = a.ts, a.step, self.t_params.data_ptr(), None
             t.seed_dev, t.sample_ids = a.seed_dev, a.sample_ids
             t.B, t.L, t.num_steps, t.sample_bb = B, L, num_steps, a.sample_bb
+        # steered calls (pf_sampler_steer after the step kernel): parameters, group structure, number of groups, the uniforms, the
+        # log-weights and the records live in buffers THIS sampler owns.  A call only rewrites their contents (set_steer, init_state),
+        # so the captured graphs keep serving; whether the uniforms are supplied is part of the launch key.
+        self.steer = bool(steer)
+        if self.steer:
+            assert self.guide, "a steered sampler weights its particles by the guidance energies: guide=True"
+            f8 = torch.float64
+            self.s_params, self.s_ngroups = e(_capi.STEER_NPARAMS, dt=f8), e(1, dt=torch.int32)
+            self.s_group_ptr, self.s_members = e(B + 1, dt=torch.int32), e(B, dt=torch.int32)
+            self.s_logw, self.s_eprev, self.s_u = e(B, dt=f8), e(B, dt=f8), e(num_steps, B, dt=f8)
+            self.s_anc, self.s_code = e(num_steps, B, dt=torch.int32), e(num_steps, B, dt=torch.int32)
+            self.s_logw_rec, self.s_ess = e(num_steps, B, dt=f8), e(num_steps, B, dt=f8)
+            self._steer_host = None
+            q = self.sargs = _capi.SamplerSteerArgs()
+            q.energy, q.ts, q.step, q.params = self.g_energy.data_ptr(), a.ts, a.step, self.s_params.data_ptr()
+            q.group_ptr, q.members, q.n_groups = self.s_group_ptr.data_ptr(), self.s_members.data_ptr(), self.s_ngroups.data_ptr()
+            q.logw, q.eprev, q.u = self.s_logw.data_ptr(), self.s_eprev.data_ptr(), None
+            q.seed_dev, q.sample_ids = a.seed_dev, a.sample_ids
+            q.ancestors, q.logw_rec, q.ess, q.code = self.s_anc.data_ptr(), self.s_logw_rec.data_ptr(), self.s_ess.data_ptr(), self.s_code.data_ptr()
+            q.rot_t, q.trans_t, q.ang_t, q.seq_t = a.rot_t, a.trans_t, a.ang_t, a.seq_t
+            q.simplex_t, q.trans0, q.simplex0 = a.simplex_t, a.trans0, a.simplex0
+            q.B, q.L, q.num_steps, q.max_group = B, L, num_steps, 1
         self.graph = None
         self.graph_k = None
         self._graph_key = None
@@ -531,6 +733,8 @@ class DeviceSampler:
         self.args.seed, self.args.first_sample = int(seed) & (2 ** 64 - 1), int(first_sample)
         if self.temper:                                 # (the noise kernel reads the key exactly as the step kernel does)
             self.targs.seed, self.targs.first_sample = self.args.seed, self.args.first_sample
+        if self.steer:
+            self.sargs.seed, self.sargs.first_sample = self.args.seed, self.args.first_sample
         self.seed_dev.copy_(torch.tensor([s, int(first_sample)], dtype=torch.int64))
         self.sample_ids.copy_(torch.arange(self.eng.B, dtype=torch.int64) + int(first_sample))
 
@@ -552,6 +756,8 @@ class DeviceSampler:
             key += (self.gargs.hotspots,)
         if self.temper:                                 # ... which of tau / gauss the noise kernel got (tau also decides the logits the step kernel reads)
             key += (self.targs.tau, self.targs.gauss)
+        if self.steer:                                  # ... and whether the resampling uniforms are supplied (NULL: in-kernel Philox)
+            key += (self.sargs.u,)
         return key
 
     def set_grid(self, grid):
@@ -609,6 +815,41 @@ class DeviceSampler:
         self.targs.tau = self.t_tau.data_ptr() if tau is not None else None
         self.args.pred_logits = self.t_logits.data_ptr() if tau is not None else self._logits_ptr
 
+    def set_steer(self, steer):
+        """The call's steering (sampler.make_steer / fit_steer) into the owned buffers; the log-weights, eprev and the records start
+        from zero, the ancestor record from the identity."""
+        assert self.steer, "a sampler built without steer=True has no steering buffers"
+        B = self.eng.B
+        assert steer["members"].shape == (B,) and steer["group_ptr"].shape == (B + 1,), steer["members"].shape
+        self.s_params.copy_(steer["params"])
+        self.s_group_ptr.copy_(steer["group_ptr"])
+        self.s_members.copy_(steer["members"])
+        self.s_ngroups.fill_(int(steer["n_groups"]))
+        self.sargs.max_group = int(steer["max_group"])
+        self._steer_host = steer
+        self._reset_steer()
+
+    def _reset_steer(self):
+        """a run starts from zero log-weights, zero eprev and empty records; the ancestor record from the identity"""
+        for buf in (self.s_logw, self.s_eprev, self.s_logw_rec, self.s_ess, self.s_code):
+            buf.zero_()
+        self.s_anc.copy_(torch.arange(self.eng.B, dtype=torch.int32).expand(self.N, self.eng.B))
+
+    def steering(self):
+        """The records of a steered run as CPU tensors: ancestors int64 [num_steps, B] (local sample index; steer_lineage reads a
+        particle's path from it), logw [num_steps, B] (after each step's update, before a reset), ess and code [num_steps, G] (0 no
+        moment, 1 a moment above the threshold, 2 resampled, -1 degenerate), groups int64 [B] (group number of every sample) and
+        weights [B]: the FINAL log-weights normalised per group, for the weighted ensemble (there is no resampling at the last step)."""
+        st = self._steer_host
+        G, of = st["n_groups"], st["group_of"].to(torch.int64)
+        logw = self.s_logw.cpu()
+        top = torch.full((G,), -math.inf, dtype=torch.float64).scatter_reduce(0, of, logw, "amax")
+        w = torch.where(torch.isfinite(top)[of], torch.exp(logw - top[of]), torch.zeros_like(logw))
+        tot = torch.zeros(G, dtype=torch.float64).index_add_(0, of, w)
+        return {"ancestors": self.s_anc.cpu().to(torch.int64), "logw": self.s_logw_rec.cpu(), "ess": self.s_ess.cpu()[:, :G].contiguous(),
+                "code": self.s_code.cpu()[:, :G].contiguous(), "groups": of.clone(), "group_ids": st["group_ids"].clone(),
+                "weights": torch.where(tot[of] > 0, w / tot[of], torch.full_like(w, math.nan))}
+
     def guidance(self):
         """The records of a guided run as CPU tensors: energy [num_steps, B, 5] (the terms of every step's UNGUIDED prediction, in the
         order of GUIDE_TERMS), shift_max [num_steps, B].  Raises if the kernel refused a restraint index."""
@@ -645,6 +886,13 @@ class DeviceSampler:
                 if self.N > 1:
                     self.t_gauss.copy_(g.reshape(self.t_gauss.shape))
             self.targs.gauss = self.t_gauss.data_ptr() if g is not None else None
+        if self.steer:                                 # pre-drawn resampling uniforms [num_steps, G] (column = group), or NULL: the kernel draws
+            u = noise.get("resample_u")
+            if u is not None:
+                assert tuple(u.shape) == (self.N, self._steer_host["n_groups"]), u.shape
+                self.s_u[:, :u.shape[1]].copy_(u.to(torch.float64))
+            self.sargs.u = self.s_u.data_ptr() if u is not None else None
+            self._reset_steer()                        # (a run that starts over, e.g. after the buckets' calibration probes, starts its weights over)
         if self.cond:
             rc = self.lib.pf_sampler_init_cond(C.byref(self.args), C.byref(self.cargs), rot0.data_ptr(), tr0.data_ptr(), ang0.data_ptr(),
                                                sx0.data_ptr(), _capi.stream_ptr())
@@ -673,6 +921,9 @@ class DeviceSampler:
         else:
             rc = self.lib.pf_sampler_step(C.byref(self.args), _capi.stream_ptr())
             _capi.check(rc, "pf_sampler_step")
+        if self.steer:                                  # weigh the particles by this step's energies; resample the state the next step starts from
+            rc = self.lib.pf_sampler_steer(C.byref(self.sargs), _capi.stream_ptr())
+            _capi.check(rc, "pf_sampler_steer")
 
     SKIP_CONTEXT_ROWS = True  # the last block's tail only produces the generated residues' predictions (set_context)
     CONCURRENT = False        # projection(b + 1) on a side stream beside EdgeTransition(b): measured slower (DenoiseEngine.run)
