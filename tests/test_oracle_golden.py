@@ -281,6 +281,139 @@ def test_oracle_autograd_matches_reference_parameter_gradients(f4, seeded_sd, go
     print("oracle autograd vs reference gradients, worst max-normalised error:", worst)
 
 
+# ---------------------------------------------------------------- golden F17 - F19: the reference at production lengths
+def _S():
+    import sys
+    sys.path.insert(0, os.path.dirname(__file__))
+    import ref_shapes
+    return ref_shapes
+
+
+_PARTS = {}
+
+
+def _parts(golden_dir, stem):
+    if stem not in _PARTS:
+        _PARTS[stem] = _S().load_parts(golden_dir, stem)
+    return _PARTS[stem]
+
+
+def _ids(shapes):
+    return [f"{B}x{L}" for B, L, _ in shapes]
+
+
+def test_reference_shape_batches_equal_their_generators(golden_dir):
+    """Every batch stored in F17 / F18 / F19 is what its synth seed builds today (tests/ref_shapes.py), the stored query rows are
+    the ones the tests expect, and no fixture file is above the size limit of a committed file."""
+    S = _S()
+    for shapes, stem, make in ((S.F17_SHAPES, "f17_", S.f17_batch), (S.F18_SHAPES, "f18_", S.f18_batch), (S.F19_SHAPES, "f19_", None)):
+        for B, L, lengths in shapes:
+            f = _parts(golden_dir, stem + S.tag(B, L))
+            made = make(B, L, lengths) if make else S.f19_batch(B, L, lengths, int(f["cand"]))
+            stored = S.batch_of(f)
+            assert set(made) == set(stored), (stem, B, L)
+            for k in made:
+                assert made[k].dtype == stored[k].dtype and torch.equal(made[k], stored[k]), (stem, B, L, k)
+            assert stored["res_mask"].sum(1).tolist() == lengths
+            if stem == "f17_":
+                assert torch.equal(f["rows"], S.query_rows(L, lengths))
+            if stem == "f18_":
+                assert f["margin"].item() >= S.F18_MIN_MARGIN
+                noise = S.synth.make_noise(B, L, S.F18_STEPS, seed=int(f["noise_seed"]))
+                assert all(torch.equal(noise[k], f[k]) for k in ("rot0", "trans0", "ang0", "simplex0"))
+    import glob
+    files = [p for s in ("f17", "f18", "f19") for p in glob.glob(os.path.join(golden_dir, s + "_*.npz"))]
+    assert len(files) >= 6 * 4 + 3 + 2 and all(os.path.getsize(p) <= S.MAX_FILE_BYTES for p in files)
+
+
+@pytest.mark.parametrize("B,L,lengths", _S().F17_SHAPES, ids=_ids(_S().F17_SHAPES))
+def test_encode_and_step_at_reference_shapes(golden_dir, seeded_sd, B, L, lengths):
+    """The restatement against the reference at the lengths where the engine runs its production plans (golden F17): encode() at
+    1e-6 (node embedding in full, edge embedding on the stored query rows), then one denoise step -- outputs, the node state and
+    the backbone update of every block, the pair state after block 4 on the stored rows -- each within 10 x the distance the
+    generator measured for that tensor (`ref_vs_oracle_*`, at most 2e-5)."""
+    S = _S()
+    f = _parts(golden_dir, "f17_" + S.tag(B, L))
+    b, rows = S.batch_of(f), f["rows"]
+    valid = b["res_mask"]
+    R1, x1, ang1, seq1, node, edge = O.encode(seeded_sd, b)
+    assert S.maxnorm(node, f["enc_node"]) <= 1e-6
+    assert S.maxnorm(S.take_rows(edge, rows), f["enc_edge_rows"]) <= 1e-6
+    col = {}
+    R, x, ang, logits = O.ga_encoder(seeded_sd, f["t"], f["R_t"], f["x_t"], f["ang_t"], f["seq_t"], node, edge, valid.long(), collect=col)
+
+    def bar(name):
+        d = f["ref_vs_oracle_" + name].item()
+        assert d <= S.ORACLE_CEILING, (name, d)
+        return min(10 * d, S.ORACLE_CEILING)
+    got = {"out_R": S.maxnorm(R[valid], f["out_R"][valid]), "out_x": S.maxnorm(x[valid], f["out_x"][valid]),
+           "out_logits": S.maxnorm(logits[valid], f["out_logits"][valid]), "out_ang": S.circle(ang[valid], f["out_ang"][valid])}
+    for blk in range(6):
+        got[f"s_blk_{blk}"] = S.maxnorm(col[f"s_{blk}"][valid], f[f"s_blk_{blk}"][valid])
+        got[f"bbupd_{blk}"] = S.maxnorm(col[f"upd_{blk}"][valid], f[f"bbupd_{blk}"][valid])
+    em = S.take_rows((valid[:, None, :] & valid[:, :, None])[..., None].expand(B, L, L, 64), rows)
+    got["z_blk_4"] = S.maxnorm(S.take_rows(col["z_4"], rows)[em], f["z_blk_4_rows"][em])
+    assert (f["z_blk_4_rows"][~em] == 0).all()
+    for name, err in got.items():
+        assert err <= bar(name), (name, err, bar(name))
+
+
+@pytest.mark.parametrize("B,L,lengths", _S().F18_SHAPES, ids=_ids(_S().F18_SHAPES))
+def test_sample_at_reference_shapes(golden_dir, seeded_sd, B, L, lengths):
+    """The restatement's sampler against the reference's 3-step sample() with recorded RNG (golden F18), as
+    test_sample_teacher_forced compares F3."""
+    S = _S()
+    f = _parts(golden_dir, "f18_" + S.tag(B, L))
+    b, ns = S.batch_of(f), S.F18_STEPS
+    traj = O.sample(seeded_sd, b, {k: f[k] for k in S.NOISE_KEYS}, ns)
+    flips = sum((traj[i]["seqs"] != f[f"step{i}_seqs"]).sum().item() for i in range(ns))
+    assert flips == 0, f"{flips} discrete sequence flips"
+    for i in range(ns):
+        close(traj[i]["rotmats"], f[f"step{i}_rotmats"], atol=2e-4)
+        close(traj[i]["trans"], f[f"step{i}_trans"], atol=5e-4, rtol=1e-4)
+        d = (traj[i]["angles"] - f[f"step{i}_angles"]).abs()
+        assert torch.minimum(d, 2 * torch.pi - d).max() < 1e-3
+        assert torch.equal(traj[i]["seqs_simplex"], f[f"step{i}_seqs_simplex"])
+
+
+@pytest.mark.parametrize("B,L,lengths", _S().F19_SHAPES, ids=_ids(_S().F19_SHAPES))
+def test_training_step_at_reference_shapes(golden_dir, seeded_sd, B, L, lengths):
+    """Losses and every parameter gradient of the restatement against the reference's training step (golden F19), as
+    test_training_forward_losses and test_oracle_autograd_matches_reference_parameter_gradients compare F4 / F6; and the condition
+    the generator chose the seed by."""
+    import json
+    from grad_probe import probe
+    S = _S()
+    f = _parts(golden_dir, "f19_" + S.tag(B, L))
+    names = json.load(open(os.path.join(golden_dir, "f6_param_names.json")))
+    lvl = dict(zip(names, f["param_fp32_noise"].tolist()))
+    loose = {n for n, v in lvl.items() if v > S.F19_LOOSE_NOISE and not n.endswith("linear_b.bias")}
+    assert bool(f["condition_met"]) and len(loose) <= S.F19_MAX_LOOSE and S.F19_DISTCOEF in loose, sorted(loose)
+    assert f["draw_gap"].item() >= S.F18_MIN_MARGIN
+    noise = {k: f[k] for k in S.TRAIN_NOISE_KEYS}
+    grads, losses = oracle_param_grads(seeded_sd, S.batch_of(f), noise)
+    assert set(losses) == {k[5:] for k in f if k.startswith("loss_")} and len(losses) == 6
+    for k, v in losses.items():
+        ref = f["loss_" + k].item()
+        assert abs(v.item() - ref) <= 2e-6 * abs(ref), (k, v.item(), ref)
+    assert len(names) == 407 and set(names) == set(grads)
+    worst = (0.0, None)
+    for i, n in enumerate(names):
+        g = grads[n]
+        if n.endswith("linear_b.bias"):                      # analytically zero (softmax shift invariance): rounding noise
+            assert g.abs().max() < 2e-5
+            continue
+        if f"pg_{i}" in f:
+            err = ((g - f[f"pg_{i}"]).abs().max() / f[f"pg_{i}"].abs().max()).item()
+        else:
+            pr, smp = probe(g.reshape(-1), i)
+            err = max(((smp - f[f"ps_{i}"]).abs().max() / f[f"ps_{i}"].abs().max()).item(),
+                      ((pr - f[f"pp_{i}"]).abs().max() / f["param_gradnorms"][i]).item())
+        worst = max(worst, (err, n))
+        assert err < 1e-4, (n, err)
+    print("oracle autograd vs reference gradients at", (B, L), "worst max-normalised error:", worst)
+
+
 def _rigid_tables():
     d = np.load(os.path.join(os.path.dirname(__file__), "..", "pepflowww_amd", "data", "rigid_groups.npz"))
     return {k: torch.from_numpy(d[k]) for k in d.files if d[k].dtype.kind != "U"}
