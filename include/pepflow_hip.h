@@ -945,8 +945,11 @@ int pf_quat_to_rot_bwd(const float* quat, const float* g_rot, float* g_quat, int
  *                       (d/d trans 3 | d/d rot 9 of the inverse-frame projection), g_gamma_rows [rows,8]
  *   pf_ipa_bwd_pairs -> g_bias [pairs,8], g_pz [pairs,16], g_z [pairs,64] (+= if accumulate_gz)
  *   host GEMMs (pf_gemm_f32, batched over sample x head): g_q = s_qk gA K, g_k = s_qk gA^T Q, g_v = P^T g_o into
- *                       g_proj[:, :3072]; g_qp = gA KP, g_kp = gA^T QP [rows,192], g_vp = P^T g_opt [rows,288]
- *   pf_ipa_bwd_points -> g_proj[:, 3072:3744] (raw point projections) and += g_frame_rows (point transforms)
+ *                       g_proj[:, :3072]; g_vp = P^T g_opt [rows,288]; g_qp [rows,192] = sum_j gA (kp_j - qp_i) (= gA KP, the rows
+ *                       of gA sum to zero): written by pf_ipa_bwd_softmax from the differences, or by a product after
+ *                       pf_ipa_bwd_rows
+ *   pf_ipa_bwd_points -> g_proj[:, 3072:3744] (raw point projections) and += g_frame_rows (point transforms); the key points'
+ *                       sum_i gA (qp_i - kp_j) is formed here from gA (g_kp is not read; the field keeps the layout)
  *   pf_ipa_headw_bwd  -> d/d head_weights [8] from the column sum of g_gamma_rows */
 typedef struct {
     const float* proj; int ldp; const float* qp; const float* kp; const float* vp; const float* z;
@@ -955,7 +958,7 @@ typedef struct {
     const float* g_feats;
     float* P; float* gA; float* g_opt; float* g_frame_rows; float* g_gamma_rows;
     float* g_bias; float* g_pz; float* g_z; int accumulate_gz;
-    const float* g_qp; const float* g_kp; const float* g_vp; float* g_proj;
+    float* g_qp; const float* g_kp; const float* g_vp; float* g_proj;
     int B, L;
     /* optional (pf_ipa_bwd_pairs): [pairs,24] = g_bias (8) | g_pz (16) per pair in ONE tensor instead of g_bias / g_pz (which may
      * then be NULL): the parameter gradients of linear_b and down_z (ipa_pytorch.py:352,355) become one [24,64] product over z */
@@ -965,7 +968,7 @@ int pf_ipa_bwd_rows(const pf_ipa_bwd_args* a, pf_stream_t stream);
 /* the same stage from SAVED probabilities (a->P written by pf_ipa_attn_fwd, p_out) and batched GEMMs issued by the host
  * (pepflowww_amd/backward.py):  pf_ipa_bwd_opt: a->g_opt holds o_pt in the global frame (= P vp) on entry and its gradient
  * on return, + g_frame_rows;  pf_ipa_bwd_pairterm: a->gA (holding g_P so far) += (W_dz^T g_o_pair) . z;
- * pf_ipa_bwd_softmax: a->gA = P (g_P - sum_j P g_P) in place, + g_gamma_rows. */
+ * pf_ipa_bwd_softmax: a->gA = P (g_P - sum_j P g_P) in place, + g_gamma_rows, + g_qp when given. */
 int pf_ipa_bwd_opt(const pf_ipa_bwd_args* a, pf_stream_t stream);
 int pf_ipa_bwd_pairterm(const pf_ipa_bwd_args* a, pf_stream_t stream);
 int pf_ipa_bwd_softmax(const pf_ipa_bwd_args* a, pf_stream_t stream);

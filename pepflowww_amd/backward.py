@@ -661,7 +661,7 @@ class IpaBlock:
         acc_z = g_z is not None
         if g_z is None:
             g_z = e(rows * L, 64)
-        g_qp, g_kp, g_vp = e(rows, 192), e(rows, 192), e(rows, 288)
+        g_qp, g_vp = e(rows, 192), e(rows, 288)
         g_proj = e(rows, 3744)
         a = _capi.IpaBwdArgs()
         a.proj, a.ldp, a.qp, a.kp, a.vp, a.z = sv["proj"].data_ptr(), 3744, sv["qp"].data_ptr(), sv["kp"].data_ptr(), sv["vp"].data_ptr(), sv["z"].data_ptr()
@@ -674,7 +674,7 @@ class IpaBlock:
         else:
             a.g_bias, a.g_pz = g_bias.data_ptr(), g_pz.data_ptr()
         a.g_z, a.accumulate_gz = g_z.data_ptr(), int(acc_z)
-        a.g_qp, a.g_kp, a.g_vp, a.g_proj, a.B, a.L = g_qp.data_ptr(), g_kp.data_ptr(), g_vp.data_ptr(), g_proj.data_ptr(), B, L
+        a.g_qp, a.g_vp, a.g_proj, a.B, a.L = g_qp.data_ptr(), g_vp.data_ptr(), g_proj.data_ptr(), B, L
         st = _capi.stream_ptr()
         LL, ldp = L * L, 3744
         bAh = (8 * LL, LL)                                  # gA / P slices: sample, head
@@ -690,18 +690,18 @@ class IpaBlock:
         _capi.check(lib.pf_ipa_bwd_pairterm(C.byref(a), st), "pf_ipa_bwd_pairterm")
         _capi.check(lib.pf_ipa_bwd_softmax(C.byref(a), st), "pf_ipa_bwd_softmax")
         _capi.check(lib.pf_ipa_bwd_pairs(C.byref(a), st), "pf_ipa_bwd_pairs")
-        # six independent sample x head products in one launch (the transposed-operand ones first: they are the longer chains)
+        # four independent sample x head products in one launch (the transposed-operand ones first: they are the longer chains).  The
+        # query / key point gradients sum_j gA (kp_j - qp_i), sum_i gA (qp_i - kp_j) are NOT products gA KP, gA^T QP over the
+        # global-frame coordinates: pf_ipa_bwd_softmax / pf_ipa_bwd_points form them from the differences (csrc/ipa_bwd.hip)
         _gemm_group([
             # g_k[b,j,h,:] = s_qk gA[b,h]^T Q[b,:,h,:]
             _gemm_args(gA, 1, L, sv["proj"], ldp, 1, g_proj, L, 128, L, alpha=S_QK, ldc=ldp, c_off=1024, batch=(B, 8, bAh, (L * ldp, 128), (L * ldp, 256))),
             # g_v[b,j,h,:] = P[b,h]^T g_o[b,:,h,:]
             _gemm_args(P, 1, L, g_feats, 1536, 1, g_proj, L, 128, L, ldc=ldp, c_off=1024 + 128, batch=(B, 8, bAh, (L * 1536, 128), (L * ldp, 256))),
-            # point contractions (global frame): gA^T QP, P^T g_opt, gA KP
-            _gemm_args(gA, 1, L, sv["qp"], 192, 1, g_kp, L, 24, L, ldc=192, batch=(B, 8, bAh, (L * 192, 24), (L * 192, 24))),
+            # value points (global frame): P^T g_opt
             _gemm_args(P, 1, L, g_opt, 288, 1, g_vp, L, 36, L, ldc=288, batch=(B, 8, bAh, (L * 288, 36), (L * 288, 36))),
             # g_q[b,i,h,:] = s_qk gA[b,h] K[b,:,h,:]            (A: [L x L] row-major; B(k=j, n=c) = proj[(b,j), 1024 + 256 h + c])
-            _gemm_args(gA, L, 1, sv["proj"], ldp, 1, g_proj, L, 128, L, alpha=S_QK, ldc=ldp, b_off=1024, batch=(B, 8, bAh, (L * ldp, 256), (L * ldp, 128))),
-            _gemm_args(gA, L, 1, sv["kp"], 192, 1, g_qp, L, 24, L, ldc=192, batch=(B, 8, bAh, (L * 192, 24), (L * 192, 24)))])
+            _gemm_args(gA, L, 1, sv["proj"], ldp, 1, g_proj, L, 128, L, alpha=S_QK, ldc=ldp, b_off=1024, batch=(B, 8, bAh, (L * ldp, 256), (L * ldp, 128)))])
         _capi.check(lib.pf_ipa_bwd_points(C.byref(a), st), "pf_ipa_bwd_points")
         # parameters of the pair projections: dW_b = g_bias^T z, dW_dz = g_pz^T z (K = pairs)
         if g_bp is not None:       # both in ONE [24,64] product over z (one pass over the pair tensor instead of two)

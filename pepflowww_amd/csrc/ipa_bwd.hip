@@ -9,10 +9,10 @@
 //                       d/d gamma [rows,8]
 //   pf_ipa_bwd_pairs  : per pair: g_bias = sqrt(1/3) g_a [pairs,8], g_pz = sum_h P g_o_pair [pairs,16],
 //                       g_z (+)= W_b^T g_bias + W_dz^T g_pz
-//   pf_ipa_bwd_points : per residue: global-frame point gradients (from the GEMMs) -> raw projection gradients
-//                       (R^T g_p), frame gradients (sum g_p, g_p (x) raw), incl. the key-side column-sum term
+//   pf_ipa_bwd_points : per residue: global-frame point gradients (query: pf_ipa_bwd_softmax, key: formed here from gA, value:
+//                       GEMM) -> raw projection gradients (R^T g_p), frame gradients (sum g_p, g_p (x) raw)
 //   pf_ipa_headw_bwd  : d/d head_weights from d/d gamma (softplus)
-// The remaining contractions (g_q, g_k, g_v, point GEMMs, dW_b, dW_dz) are pf_gemm_f32 calls issued by the host
+// The remaining contractions (g_q, g_k, g_v, the value-point GEMM, dW_b, dW_dz) are pf_gemm_f32 calls issued by the host
 // (pepflowww_amd/backward.py: ipa_backward).
 #include "common.h"
 #include "../../include/pepflow_hip.h"
@@ -229,25 +229,40 @@ __global__ __launch_bounds__(256) void ipa_bwd_pairs_kernel(pf_ipa_bwd_args a) {
 
 // One workgroup per residue row r = (b, j), one thread per (head, point) -- 8 x (8 query + 8 key + 12 value) = 224 of the 256: the raw
 // projections and their gradients are then read / written along the 672 point columns of ONE row (coalesced), the twelve frame-gradient
-// sums of the row are a workgroup reduction (no atomics), and the column sums c_hj = sum_i g_a_hij of the row's eight heads are formed
-// first by all 256 threads (four strided loads each, all in flight).  (One thread per (sample, head, residue) walked its 28 points
+// sums of the row are a workgroup reduction (no atomics), and the key-point gradients sum_i g_a_hij (qp_i - kp_j) of the row's eight
+// heads are formed first by all 256 threads (32 lanes per head over the queries).  (One thread per (sample, head, residue) walked its 28 points
 // serially with every lane of a wave in a different row: ~250 uncoalesced 4-byte accesses in a dependent chain, 37 us per launch.)
 __global__ __launch_bounds__(256) void ipa_bwd_points_kernel(pf_ipa_bwd_args a) {
-    __shared__ float CS[H];
+    __shared__ float GK[H][24];
     __shared__ float FR[4][12];
     const int L = a.L, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = blockIdx.x, b = r / L, j = r - b * L;
     {
+        // key points: sum_i g_a_hij (qp_i - kp_j), 32 lanes per head over the queries i.  The DIFFERENCE is formed before the
+        // product: gA^T QP - (sum_i g_a_hij) kp_j, two sums of the size of the coordinates, lost |x| / |qp_i - kp_j| of the fp32
+        // mantissa (translations of +-25: d/d trans off by 1e-5 of its largest entry, 30 x an fp32 autograd's error)
         const int h = tid >> 5, l32 = tid & 31;
         const float* ga = a.gA + (((size_t)b * H + h) * L) * L + j;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int i = l32;
-        for (; i + 96 < L; i += 128) {
-            s0 += ga[(size_t)i * L]; s1 += ga[(size_t)(i + 32) * L]; s2 += ga[(size_t)(i + 64) * L]; s3 += ga[(size_t)(i + 96) * L];
+        const float4* kj = reinterpret_cast<const float4*>(a.kp + (size_t)r * 192 + h * 24);
+        float4 k[6], acc[6];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) { k[c] = kj[c]; acc[c] = make_float4(0.f, 0.f, 0.f, 0.f); }
+#pragma unroll 2
+        for (int i = l32; i < L; i += 32) {
+            const float g = ga[(size_t)i * L];
+            const float4* qi = reinterpret_cast<const float4*>(a.qp + ((size_t)b * L + i) * 192 + h * 24);
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+                const float4 q = qi[c];
+                acc[c].x += g * (q.x - k[c].x); acc[c].y += g * (q.y - k[c].y); acc[c].z += g * (q.z - k[c].z); acc[c].w += g * (q.w - k[c].w);
+            }
         }
-        for (; i < L; i += 32) s0 += ga[(size_t)i * L];
-        const float s = sum_xor16(row16_sum((s0 + s1) + (s2 + s3)));        // over the 32 lanes of this head
-        if (l32 == 0) CS[h] = s;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {                                           // over the 32 lanes of this head
+            const float sx = sum_xor16(row16_sum(acc[c].x)), sy = sum_xor16(row16_sum(acc[c].y));
+            const float sz = sum_xor16(row16_sum(acc[c].z)), sw = sum_xor16(row16_sum(acc[c].w));
+            if (l32 == 0) { GK[h][4 * c] = sx; GK[h][4 * c + 1] = sy; GK[h][4 * c + 2] = sz; GK[h][4 * c + 3] = sw; }
+        }
     }
     __syncthreads();
     float fr[12];
@@ -261,17 +276,15 @@ __global__ __launch_bounds__(256) void ipa_bwd_points_kernel(pf_ipa_bwd_args a) 
         const float gamma = softplusf(a.head_w[h]) * S_PT;
         float gp[3], raw[3];
         int col, ms;                                            // the point's x column, stride between x / y / z
-        if (q < PQ) {                                           // query points: g = gamma * (g_a KP)
+        if (q < PQ) {                                           // query points: g = gamma * sum_j g_a (kp_j - qp_i)
             col = 3072 + h * PQ + q; ms = 64;
 #pragma unroll
             for (int m = 0; m < 3; ++m) gp[m] = gamma * a.g_qp[(size_t)r * 192 + h * 24 + q * 3 + m];
-        } else if (q < 2 * PQ) {                                // key points: g = gamma * (g_a^T QP - c kp)
+        } else if (q < 2 * PQ) {                                // key points: g = gamma * sum_i g_a (qp_i - kp_j)
             const int p = q - PQ;
             col = 3264 + h * (PQ + PV) + p; ms = 160;
-            const float csum = CS[h];
 #pragma unroll
-            for (int m = 0; m < 3; ++m)
-                gp[m] = gamma * (a.g_kp[(size_t)r * 192 + h * 24 + p * 3 + m] - csum * a.kp[(size_t)r * 192 + h * 24 + p * 3 + m]);
+            for (int m = 0; m < 3; ++m) gp[m] = gamma * GK[h][p * 3 + m];
         } else {                                                // value points
             const int p = q - 2 * PQ;
             col = 3264 + h * (PQ + PV) + PQ + p; ms = 160;
@@ -386,7 +399,7 @@ __global__ __launch_bounds__(256) void ipa_bwd_pairterm_kernel(pf_ipa_bwd_args a
 }
 
 // pf_ipa_bwd_softmax: one wave per (b, h, i):  g_a = P (g_P - sum_j P g_P) in place in gA;  g_gamma_rows[(b,i), h] =
-// -1/2 sum_j g_a sum_p |qp_i - kp_j|^2
+// -1/2 sum_j g_a sum_p |qp_i - kp_j|^2;  g_qp[(b,i), h] = sum_j g_a (kp_j - qp_i) from the same differences
 __global__ __launch_bounds__(256) void ipa_bwd_softmax_kernel(pf_ipa_bwd_args a) {
     const int L = a.L;
     const long long wr = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -404,6 +417,9 @@ __global__ __launch_bounds__(256) void ipa_bwd_softmax_kernel(pf_ipa_bwd_args a)
 #pragma unroll
     for (int c = 0; c < 24; ++c) q[c] = qp[c];
     float gg = 0.f;
+    float gq[24];                                       // sum_j g_a (kp_j - qp_i): the query points' gradient over gamma
+#pragma unroll
+    for (int c = 0; c < 24; ++c) gq[c] = 0.f;
     for (int j = lane; j < L; j += 64) {
         const float ga = P[j] * (gA[j] - dl);
         gA[j] = ga;
@@ -414,11 +430,21 @@ __global__ __launch_bounds__(256) void ipa_bwd_softmax_kernel(pf_ipa_bwd_args a)
             const float4 k4 = *reinterpret_cast<const float4*>(kp + 4 * c4);
             const float d0 = q[4 * c4] - k4.x, d1 = q[4 * c4 + 1] - k4.y, dd = q[4 * c4 + 2] - k4.z, d3 = q[4 * c4 + 3] - k4.w;
             d2 += d0 * d0; d2 += d1 * d1; d2 += dd * dd; d2 += d3 * d3;
+            gq[4 * c4] -= ga * d0; gq[4 * c4 + 1] -= ga * d1; gq[4 * c4 + 2] -= ga * dd; gq[4 * c4 + 3] -= ga * d3;
         }
         gg += ga * d2;
     }
     gg = wave_sum(gg);
     if (lane == 0) a.g_gamma_rows[((size_t)b * L + i) * 8 + h] = -0.5f * gg;
+    if (a.g_qp) {                                       // (wave-uniform)
+#pragma unroll
+        for (int c = 0; c < 24; ++c) gq[c] = wave_sum(gq[c]);
+        if (lane == 0) {
+            float4* o = reinterpret_cast<float4*>(a.g_qp + ((size_t)b * L + i) * 192 + h * 24);
+#pragma unroll
+            for (int c4 = 0; c4 < 6; ++c4) o[c4] = make_float4(gq[4 * c4], gq[4 * c4 + 1], gq[4 * c4 + 2], gq[4 * c4 + 3]);
+        }
+    }
 }
 
 __global__ void ipa_headw_bwd_kernel(const float* g_gamma, const float* head_w, float* g_head_w) {
@@ -474,7 +500,7 @@ extern "C" int pf_ipa_bwd_pairs(const pf_ipa_bwd_args* a, pf_stream_t stream) {
     return 0;
 }
 extern "C" int pf_ipa_bwd_points(const pf_ipa_bwd_args* a, pf_stream_t stream) {
-    if (!args_ok(a) || !a->g_qp || !a->g_kp || !a->g_vp || !a->g_proj || !a->g_frame_rows) return PF_E_BADARG;
+    if (!args_ok(a) || !a->g_qp || !a->g_vp || !a->g_proj || !a->g_frame_rows) return PF_E_BADARG;
     hipLaunchKernelGGL(ipa_bwd_points_kernel, dim3((unsigned)(a->B * a->L)), dim3(256), 0, (hipStream_t)stream, *a);
     PF_CHECK_LAUNCH();
     return 0;
