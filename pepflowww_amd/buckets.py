@@ -17,6 +17,8 @@ from types import SimpleNamespace
 
 import torch
 
+from .sampler import DeviceSampler, SampleCall, _fit, _rows, fit_cond, fit_guide, fit_steer, fit_temper, make_grid
+
 FUSED_MAX_L = 128        # longest padded length of the projection-inside score kernel (pf_ipa_proj_inside_ok)
 
 
@@ -43,29 +45,6 @@ def plan_length_buckets(lengths, edges=(FUSED_MAX_L,), quantum=16):
     return [(g, max(pad[i] for i in g)) for g in groups if g]
 
 
-def _rows(v, idx, axis=0):
-    """v[idx] along `axis`: device tensors by one GPU gather, host tensors through numpy (torch's CPU ops fork an OpenMP team beyond 32 k
-    elements, which was measured at 20 - 200 ms in a process with a large idle thread pool: sampler.quat_to_rot_host)."""
-    if v.is_cuda:
-        return v.index_select(axis, torch.as_tensor(idx, dtype=torch.int64, device=v.device))
-    import numpy as np
-    return torch.from_numpy(np.ascontiguousarray(np.take(v.numpy(), np.asarray(idx, dtype=np.int64), axis=axis)))
-
-
-def _fit(v, L0, Lk, axis=1, value=0):
-    """Residue axis cut or padded from L0 to Lk."""
-    from .flow_model import _pad_axis1
-    if Lk == L0:
-        return v
-    if Lk < L0:
-        return v.narrow(axis, 0, Lk).contiguous()
-    if axis == 1:
-        return _pad_axis1(v, Lk - L0, value)
-    lead = tuple(v.shape[:axis - 1])                     # ([2N, B, L0, 20]: fold the leading axis, pad, unfold)
-    w = _pad_axis1(v.reshape((-1,) + tuple(v.shape[axis:])), Lk - L0, value)
-    return w.reshape(lead + tuple(v.shape[axis - 1:axis]) + (Lk,) + tuple(v.shape[axis + 1:]))
-
-
 def sub_batch(batch, idx, L0, Lk):
     """The samples `idx` of a PaddingCollate-style batch at padded length Lk (pad values as PaddingCollate: zeros, aa -> 21)."""
     B = batch["aa"].shape[0]
@@ -90,7 +69,7 @@ def sub_noise(noise, idx, L0, Lk):
     for k, v in noise.items():
         if v is None:
             out[k] = None
-        elif k == "resample_u":                            # [N, G] by GROUP: BucketedSampler.bind picks the bucket's columns
+        elif k == "resample_u":                            # [N, G] by GROUP: DeviceSampler.begin picks the bucket's columns
             out[k] = v
         elif k in ("expo", "gauss"):                       # [2N, B, L0, 20] / [N-1, B, L0, 6]: the sample on axis 1
             w = _rows(v, idx, axis=1)
@@ -114,25 +93,21 @@ def sub_noise(noise, idx, L0, Lk):
 def sub_guide(guide, idx, L0, Lk):
     """The packed guidance (sampler.make_guide) of the samples `idx`: their own restraint lists and hot spots, the plane cut / padded to
     Lk; residue indices stay (padding is appended at the end)."""
-    from .sampler import fit_guide
     return fit_guide(guide, L0, Lk, idx)
 
 
 def sub_temper(temper, idx, L0, Lk):
     """The packed tempering (sampler.make_temper) of the samples `idx`: their own temperature rows, the plane cut / padded to Lk."""
-    from .sampler import fit_temper
     return fit_temper(temper, L0, Lk, idx)
 
 
 def sub_steer(steer, idx, L0, Lk):
     """The packed steering (sampler.make_steer) of the samples `idx`: their groups renumbered, the caller's numbers kept in "group_ids"."""
-    from .sampler import fit_steer
     return fit_steer(steer, L0, Lk, idx)
 
 
 def sub_cond(cond, idx, L0, Lk):
     """The packed conditioning (sampler.make_cond) of the samples `idx`, residue axis cut / padded to Lk by inert rows, like the noise."""
-    from .sampler import fit_cond
     return fit_cond(cond, L0, Lk, idx)
 
 
@@ -156,16 +131,12 @@ class BucketedSampler:
     # ---- set-up of one call ----------------------------------------------------------------------------------------------
     def bind(self, batch, noise, L0, seed, first_sample, stamp=lambda name: None, grid=None, cond=None, guide=None, temper=None, steer=None):
         """batch / noise: the caller's ([B, L0, ...], not padded).  Builds (or fetches from the encoder's cache) one engine + sampler
-        per bucket, encodes each sub-batch into its engine's pair buffer and initialises the sampler states.  grid / cond: the call's
-        time grid (None: the reference's) and packed conditioning (sampler.make_cond), sliced and padded per bucket like the noise;
-        they stay in the samplers' own buffers, so the re-initialisation after the calibration probes is the conditioned one too.
-        guide: the call's packed guidance (sampler.make_guide), sliced per bucket the same way.
-        temper: the call's packed tempering (sampler.make_temper), likewise; the pre-drawn normals follow the samples with the noise.
-        steer: the call's packed steering (sampler.make_steer): a bucket gets its own groups (members share a length, so no bucket cuts
-        a group) and the columns of noise["resample_u"] that belong to them."""
-        if grid is None:
-            from .sampler import make_grid
-            grid = make_grid(self.N)
+        per bucket, encodes each sub-batch into its engine's pair buffer and initialises the sampler states.  grid / cond / guide /
+        temper / steer: the fields of the call's SampleCall (grid None: the reference's), fitted per bucket like the noise
+        (SampleCall.fit) and bound by DeviceSampler.begin; they stay in the samplers' own buffers, so the re-initialisation after the
+        calibration probes is the conditioned one too.  A bucket gets its own steering groups (members share a length, so no bucket
+        cuts a group) and the columns of noise["resample_u"] that belong to them."""
+        call = SampleCall(make_grid(self.N) if grid is None else grid, self.flags, cond, guide, temper, steer)
         model, dev = self.model, batch["aa"].device
         self.samplers.clear()
         self.engines.clear()
@@ -184,25 +155,9 @@ class BucketedSampler:
             stamp("encode")
             eng.bind_context(node, edge, sb["res_mask"])
             stamp("bind")
-            smp = eng.sampler(self.N, self.flags, cond=cond is not None, guide=guide is not None, temper=temper is not None, steer=steer is not None)
-            smp.set_seed(seed, first_sample)
-            smp.set_grid(grid)
+            smp = eng.sampler(self.N, self.flags, **call.kinds)
             ids = torch.as_tensor(idx, dtype=torch.int64) + int(first_sample)
-            smp.set_sample_ids(ids)
-            smp.set_context(R1, x1, ang1, seq1, sb["generate_mask"])
-            if cond is not None:
-                smp.set_cond(sub_cond(cond, idx, L0, Lk), (R1, x1, ang1, seq1))
-            if guide is not None:
-                smp.set_guide(sub_guide(guide, idx, L0, Lk))
-            if temper is not None:
-                smp.set_temper(sub_temper(temper, idx, L0, Lk))
-            if steer is not None:
-                st = sub_steer(steer, idx, L0, Lk)
-                smp.set_steer(st)
-                if nz.get("resample_u") is not None:
-                    nz["resample_u"] = nz["resample_u"][:, st["group_ids"]].contiguous()
-            smp.init_state(nz)
-            self._nz.append(nz)
+            self._nz.append(smp.begin(call.fit(L0, Lk, idx), (R1, x1, ang1, seq1), sb["generate_mask"], nz, seed, first_sample, ids))
             smp.L_out = Lk
             self.samplers.append(smp)
             self.engines.append(eng)
@@ -363,7 +318,10 @@ class BucketedSampler:
             out["ess"][:, rec["group_ids"]], out["code"][:, rec["group_ids"]] = rec["ess"], rec["code"]
         return out
 
+    precision = property(lambda self: self.engines[0].precision)
+
     def operand_range(self):
+        """The buckets' engines' reports (DenoiseEngine.operand_range) as one: the largest value per buffer."""
         reps = [e.operand_range() for e in self.engines]
         out = {k: max(r[k] for r in reps) for k in reps[0] if k not in ("limit", "ok")}
         out["limit"] = reps[0]["limit"]
@@ -411,5 +369,4 @@ class BucketedSampler:
 
     def trajectory(self, pageable=False):
         """Same format as DeviceSampler.trajectory: list of N dicts of CPU tensors [B, L_out, ...] in the caller's sample order."""
-        from .sampler import DeviceSampler
         return DeviceSampler.trajectory(self, pageable=pageable)

@@ -15,6 +15,7 @@ from collections import OrderedDict
 import torch
 
 from . import _capi
+from .sampler import DeviceSampler
 
 N_BLOCKS = 6
 
@@ -760,18 +761,19 @@ class DenoiseEngine:
         sampler that launches pf_guidance_fwd in front of the step kernel (guided sampling) -- one more launch, so a different sampler.
         temper: a sampler that launches pf_sampler_temper in front of the step kernel (tempered / stochastic sampling) -- likewise.
         steer: a sampler that launches pf_sampler_steer behind the step kernel (steered sampling) -- two more launches, likewise."""
-        from .sampler import DeviceSampler
-        key = (int(num_steps), tuple(bool(f) for f in flags)) + ((True,) if cond else ()) + (("guide",) if guide else ()) + (("temper",) if temper else ()) + (("steer",) if steer else ())
+        kinds = {"cond": bool(cond), "guide": bool(guide), "temper": bool(temper), "steer": bool(steer)}      # (SampleCall.kinds)
+        # the key is (N, flags[, True][, "guide"][, "temper"][, "steer"]): one entry per kind that is on, in the order of `kinds`
+        key = (int(num_steps), tuple(bool(f) for f in flags)) + tuple(True if k == "cond" else k for k, on in kinds.items() if on)
         smp = self._samplers.get(key)
         if smp is None:
             try:
-                smp = DeviceSampler(self, num_steps, flags, cond=cond, guide=guide, temper=temper, steer=steer)
+                smp = DeviceSampler(self, num_steps, flags, **kinds)
             except torch.cuda.OutOfMemoryError:                 # trajectory buffers: drop the other samplers / engines, one retry
                 self._samplers.clear()
                 if self._owner is not None:
                     self._owner._make_room(self)
                 torch.cuda.empty_cache()
-                smp = DeviceSampler(self, num_steps, flags, cond=cond, guide=guide, temper=temper, steer=steer)
+                smp = DeviceSampler(self, num_steps, flags, **kinds)
             self._samplers[key] = smp
             while len(self._samplers) > self.SAMPLER_CACHE:
                 self._samplers.popitem(last=False)

@@ -4,32 +4,20 @@ kernels.  See INTEGRATION.md for how train.py / inference.py pick it up.
 """
 import gc
 import threading
+import time
+import warnings
 
 import torch
 from torch import nn
 
 from . import _capi, featurize
+from . import buckets as _bk
 from .modules import EdgeEmbedder, GAEncoder, NodeEmbedder
-from .sampler import (DeviceSampler, check_gauss, check_resample_u, default_noise, fit_cond, fit_guide, fit_temper, make_cond, make_guide,
-                      make_steer, make_temper)
+from .sampler import SampleCall, _pad_axis1, default_noise
 from .train_forward import TrainForward, default_train_noise
 
 MAX_NUM_HEAVYATOMS = 15     # pepflow/modules/protein/constants.py:91
 _PAD_AA = 21                # constants.PAD_RESIDUE_INDEX (pepflow/utils/data.py:9-13)
-
-
-def _pad_axis1(v, n, value=0):
-    """[B, L0, ...] -> [B, L0 + n, ...] with `value` appended along the residue axis.  Host tensors go through numpy (torch's CPU ops fork
-    an OpenMP team beyond 32 k elements: 20 - 200 ms stalls were measured on a 150 KB pad, see sampler.quat_to_rot_host), device tensors
-    through one GPU kernel."""
-    if v.is_cuda:
-        import torch.nn.functional as F
-        return F.pad(v, [0, 0] * (v.dim() - 2) + [0, n], value=value)
-    import numpy as np
-    a = v.numpy()
-    out = np.full((a.shape[0], a.shape[1] + n) + a.shape[2:], value, dtype=a.dtype)
-    out[:, :a.shape[1]] = a
-    return torch.from_numpy(out)
 
 
 def _pad_residues(batch, noise, L0, L):
@@ -227,9 +215,8 @@ class FlowModel(nn.Module):
         calibrate    (default on) length buckets only: the first bucketed call of a (device, bucket shapes) pair times a few steps on
                      candidate HIP stream assignments and keeps the first that overlaps (buckets.py); False: take the default streams;
         timings      optional dict: filled with the wall-clock seconds of the call's phases (noise / engine / encode / bind / setup /
-                     capture / loop / d2h; each phase is followed by a device synchronisation when this is given -- bench.py's
+                     capture / loop / range_check / d2h; each phase is followed by a device synchronisation when this is given -- bench.py's
                      per-call accounting)."""
-        import time
         _capi.load()
         _t = [time.perf_counter()]
 
@@ -242,30 +229,26 @@ class FlowModel(nn.Module):
         dev = batch["aa"].device
         B, L0 = batch["aa"].shape
         self.last_buckets = None                       # [(samples, padded length)] of the call when it was split by length
-        # the conditioning arguments, validated and packed on the host (sampler.make_cond): the grid of EVERY call, the three scalar
-        # switches, and `cond` = None for a call that uses none of the per-residue / partial-start arguments
-        grid, flags, cond = make_cond(B, L0, num_steps, sample_bb, sample_ang, sample_seq, t_start, ts, start, aa_allowed)
-        guide = make_guide(guide, B, L0, batch.get("generate_mask"), batch.get("res_mask"))
         self.last_guidance = None                      # the per-step energies and largest shifts of a guided call
-        temper = make_temper(temper, B, L0)
-        check_gauss(noise, temper, int(num_steps), B, L0)
-        steer = make_steer(steer, B, L0, batch, cond, guide, temper)
-        check_resample_u(noise, steer, int(num_steps))
         self.last_steering = None                      # the ancestor record, log-weights, ESS and codes of a steered call
+        # every argument that describes the call, validated and packed on the host: the grid of EVERY call, the three scalar switches,
+        # and the extensions it uses (None for the others)
+        call = SampleCall.make(batch, num_steps, sample_bb, sample_ang, sample_seq, t_start=t_start, ts=ts, start=start,
+                               aa_allowed=aa_allowed, guide=guide, temper=temper, steer=steer, noise=noise)
         if noise is None:
             if seed is None:
                 noise = default_noise(B, L0)          # torch's global CPU generator, like the reference (flow_model.py:252-277)
             else:                                      # explicit seed: per-global-sample streams (shard == slice of the full run)
                 from .distributed import seeded_noise
                 noise = seeded_noise(first_sample, first_sample + B, L0, seed)
+        tail = dict(timed=timings is not None, use_graph=use_graph, return_sampler=return_sampler, pageable=pageable, check_range=check_range,
+                    gc_collect=gc_collect, gc_was_enabled=_gc_was_enabled)
         if buckets is not None and buckets is not False and "res_mask" in batch and L0 > 16:
-            from . import buckets as _bk
             edges = (_bk.FUSED_MAX_L,) if buckets == "auto" or buckets is True else tuple(buckets)
             plan = _bk.plan_length_buckets(_bk.sample_lengths(batch["res_mask"]), edges)
             if len(plan) > 1:
-                return self._sample_bucketed(plan, batch, num_steps, flags, noise, seed, first_sample,
-                                             use_graph, return_sampler, timings, pageable, check_range, stamp, gc_collect, calibrate, _gc_was_enabled,
-                                             grid=grid, cond=cond, guide=guide, temper=temper, steer=steer)
+                smp = self._sample_bucketed(plan, batch, num_steps, noise, seed, first_sample, stamp, calibrate, **vars(call))
+                return self._run_bound(smp, call, L0, stamp, **tail)
         # Residue axis padded to a multiple of 16 internally (what PaddingCollate does to a shorter sample of a batch: pad values,
         # res_mask False -- padded residues are inert, tests/test_gpu_parity.py ragged cases): every kernel then runs its
         # full-tile path (16-row / 16-key tiles, float4 rows of the [B,8,L,L] buffers).  In-kernel random draws are keyed by
@@ -273,9 +256,7 @@ class FlowModel(nn.Module):
         L = (L0 + 15) // 16 * 16
         if L != L0:
             batch, noise = _pad_residues(batch, noise, L0, L)
-            cond = fit_cond(cond, L0, L)
-            guide = fit_guide(guide, L0, L)
-            temper = fit_temper(temper, L0, L)
+            call = call.fit(L0, L)
         stamp("noise")
         # The engine (workspaces, launch plan), its sampler (trajectory buffers, captured graphs) and the packed weights are cached
         # (GAEncoder.engine / DenoiseEngine.sampler): a second call at a shape seen before only encodes, binds and replays.
@@ -287,98 +268,63 @@ class FlowModel(nn.Module):
         stamp("bind")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        smp = eng.sampler(num_steps, flags, cond=cond is not None, guide=guide is not None, temper=temper is not None, steer=steer is not None)
-        smp.set_seed(seed, first_sample)
-        smp.set_grid(grid)
-        smp.set_context(R1, x1, ang1, seq1, batch["generate_mask"])
-        if cond is not None:
-            smp.set_cond(cond, (R1, x1, ang1, seq1))
-        if guide is not None:
-            smp.set_guide(guide)
-        if temper is not None:
-            smp.set_temper(temper)
-        if steer is not None:
-            smp.set_steer(steer)
-        smp.init_state(noise)
+        smp = eng.sampler(num_steps, call.flags, **call.kinds)
+        smp.begin(call, (R1, x1, ang1, seq1), batch["generate_mask"], noise, seed, first_sample)
         stamp("setup")
-        if use_graph and timings is not None and smp.needs_capture():
+        return self._run_bound(smp, call, L0, stamp, stream_out=not return_sampler, **tail)     # (the trajectory leaves for the host while the loop runs)
+
+    def _sample_bucketed(self, plan, batch, num_steps, noise, seed, first_sample, stamp, calibrate=True, flags=(True, True, True),
+                         grid=None, cond=None, guide=None, temper=None, steer=None):
+        """The BOUND sampler of a ragged batch's length buckets (pepflowww_amd/buckets.py): same inputs, noise, Philox streams and
+        output format as the unsplit path.  It does not sample any more, whatever the name says: _sample_impl runs _run_bound on what
+        it returns.  flags ... steer: the fields of the call's SampleCall, as keywords because BucketedSampler.bind takes them so
+        (it puts them together again); last_buckets is set here, before the loop."""
+        stamp("noise")
+        B, L0 = batch["aa"].shape
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        smp = _bk.BucketedSampler(self, plan, B, (L0 + 15) // 16 * 16, num_steps, flags)
+        smp.calibrate = bool(calibrate)
+        smp.bind(batch, noise, L0, seed, first_sample, stamp, grid=grid, cond=cond, guide=guide, temper=temper, steer=steer)
+        self.last_buckets = [(len(idx), Lk) for idx, Lk in plan]
+        return smp
+
+    def _run_bound(self, smp, call, L0, stamp, *, timed, use_graph, return_sampler, pageable, check_range, gc_collect, gc_was_enabled, **run_kw):
+        """The tail of a call, from a bound sampler (a DeviceSampler or a BucketedSampler: the same interface) to what sample() returns:
+        capture (its own phase only when the call is timed), the step loop, the collector's pass, the range verdict, the records."""
+        N, B, L = smp.N, smp.eng.B, smp.eng.L
+        if use_graph and timed and smp.needs_capture():
             smp.capture()
             stamp("capture")
-        smp.run(num_steps, use_graph=use_graph, stream_out=not return_sampler)     # (the trajectory leaves for the host while the loop runs)
+        smp.run(N, use_graph=use_graph, **run_kw)
         # The step loop is enqueued (graph replays) and the host now only waits for the device: the one place where a full pass of
         # the cyclic garbage collector costs nothing.  A call returns ~2 000 tensor / dict objects (the reference's list-of-dicts
         # trajectory), so a loop over complexes triggers full collections anyway -- 15 - 90 ms each, in whatever host phase they hit
         # (BENCH r05: three of eight warm calls, 180 of 295 ms of all overhead); collecting here, under >= ~40 ms of device work,
         # takes them out of the call's critical path.  Only when the collector is enabled at all.
-        if gc_collect and self.GC_UNDER_LOOP and B * L * L * num_steps >= self.GC_MIN_PAIR_STEPS:
-            if gc.isenabled() if _gc_was_enabled is None else _gc_was_enabled:
+        if gc_collect and self.GC_UNDER_LOOP and B * L * L * N >= self.GC_MIN_PAIR_STEPS:
+            if gc.isenabled() if gc_was_enabled is None else gc_was_enabled:
                 gc.collect()
         stamp("loop")
         if check_range:
-            # run-time range verdict of the split-precision operands (engine.operand_range: five small reductions, one host read
-            # per CALL, not per step): loud, because no trained checkpoint could be tried in this build
-            rep = eng.operand_range()
+            # run-time range verdict of the split-precision operands (engine.operand_range: five small reductions per engine, one
+            # host read per CALL, not per step): loud, because no trained checkpoint could be tried in this build
+            rep = smp.operand_range()
             self.last_range_report = rep
-            _raise_if_saturated(rep, eng.precision)
+            _raise_if_saturated(rep, smp.precision)
             if not rep["ok"]:
-                import warnings
                 warnings.warn("pepflowww_amd: activations reached " + ", ".join(f"{k}={v:.3g}" for k, v in rep.items() if k not in ("limit", "ok")) +
                               f" -- beyond half of the f16 range ({rep['limit']:g}) the hi / lo split of the MFMA operands saturates (fp32 mode) or "
                               "overflows (f16 mode) where the fp32 reference would not: results may deviate (INTEGRATION.md, numeric range)",
-                              RuntimeWarning, stacklevel=2)
+                              RuntimeWarning, stacklevel=3)       # (the frame of sample())
             stamp("range_check")
         smp.L_out = L0
-        if guide is not None:
+        if call.kinds["guide"]:
             self.last_guidance = smp.guidance()
-        if steer is not None:
+        if call.kinds["steer"]:
             self.last_steering = smp.steering()
         if return_sampler:
-            return smp                                 # (owned by the engine: the next sample() call at this shape reuses it)
-        traj = smp.trajectory(pageable=pageable)
-        stamp("d2h")
-        return traj
-
-    def _sample_bucketed(self, plan, batch, num_steps, flags, noise, seed, first_sample, use_graph, return_sampler, timings, pageable,
-                         check_range, stamp, gc_collect=True, calibrate=True, _gc_was_enabled=None, grid=None, cond=None, guide=None,
-                         temper=None, steer=None):
-        """sample() of a ragged batch through its length buckets (pepflowww_amd/buckets.py): same inputs, noise, Philox streams and
-        output format as the unsplit path.  grid / cond / guide / temper: the call's time grid, packed conditioning (sampler.make_cond),
-        packed guidance (sampler.make_guide), packed tempering (sampler.make_temper) and packed steering (sampler.make_steer)."""
-        from .buckets import BucketedSampler
-        stamp("noise")
-        B, L0 = batch["aa"].shape
-        L = (L0 + 15) // 16 * 16
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        smp = BucketedSampler(self, plan, B, L, num_steps, flags)
-        smp.calibrate = bool(calibrate)
-        smp.bind(batch, noise, L0, seed, first_sample, stamp, grid=grid, cond=cond, guide=guide, temper=temper, steer=steer)
-        if use_graph and timings is not None and smp.needs_capture():
-            smp.capture()
-            stamp("capture")
-        smp.run(num_steps, use_graph=use_graph)
-        if gc_collect and self.GC_UNDER_LOOP and B * L * L * num_steps >= self.GC_MIN_PAIR_STEPS:
-            if gc.isenabled() if _gc_was_enabled is None else _gc_was_enabled:
-                gc.collect()
-        stamp("loop")
-        if check_range:
-            rep = smp.operand_range()
-            self.last_range_report = rep
-            _raise_if_saturated(rep, getattr(self.ga_encoder, "_precision", "fp32"))
-            if not rep["ok"]:
-                import warnings
-                warnings.warn("pepflowww_amd: activations reached " + ", ".join(f"{k}={v:.3g}" for k, v in rep.items() if k not in ("limit", "ok")) +
-                              f" -- beyond half of the f16 range ({rep['limit']:g}) the split-precision operands saturate / overflow "
-                              "(INTEGRATION.md, numeric range)", RuntimeWarning, stacklevel=3)
-            stamp("range_check")
-        smp.L_out = L0
-        self.last_buckets = [(len(idx), Lk) for idx, Lk in plan]
-        if guide is not None:
-            self.last_guidance = smp.guidance()
-        if steer is not None:
-            self.last_steering = smp.steering()
-        if return_sampler:
-            return smp
+            return smp                                 # (a DeviceSampler is owned by its engine: the next sample() call at this shape reuses it)
         traj = smp.trajectory(pageable=pageable)
         stamp("d2h")
         return traj

@@ -10,6 +10,7 @@ rebuilds `t` on the host every step (288).  Here the whole loop lives on the GPU
     D2H copy at the end produces the reference's list of dicts of CPU tensors.
 """
 import ctypes as C
+import dataclasses
 import math
 import numbers
 
@@ -23,7 +24,6 @@ def quat_to_rot_host(q):
     """Unit quaternions [..., 4] -> rotation matrices [..., 3, 3] on the host, in NUMPY: torch's CPU ops fork an OpenMP team for any
     tensor beyond 32 k elements, and in a process whose (often > 100) pool threads were used elsewhere that fork was measured at 20 - 200 ms
     for a 150 KB tensor (profiles/r05/README.md, per-call stalls) -- numpy's elementwise loops stay on the calling thread."""
-    import numpy as np
     q = q.numpy() if torch.is_tensor(q) else q
     q = q / np.sqrt((q * q).sum(-1, keepdims=True))
     a, b, c, d = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
@@ -168,12 +168,43 @@ def make_cond(B, L, num_steps, sample_bb=True, sample_ang=True, sample_seq=True,
     return grid, flags, cond
 
 
+def _pad_axis1(v, n, value=0):
+    """[B, L0, ...] -> [B, L0 + n, ...] with `value` appended along the residue axis.  Host tensors go through numpy (torch's CPU ops fork
+    an OpenMP team beyond 32 k elements: 20 - 200 ms stalls were measured on a 150 KB pad, see quat_to_rot_host), device tensors
+    through one GPU kernel."""
+    if v.is_cuda:
+        return torch.nn.functional.pad(v, [0, 0] * (v.dim() - 2) + [0, n], value=value)
+    a = v.numpy()
+    out = np.full((a.shape[0], a.shape[1] + n) + a.shape[2:], value, dtype=a.dtype)
+    out[:, :a.shape[1]] = a
+    return torch.from_numpy(out)
+
+
+def _rows(v, idx, axis=0):
+    """v[idx] along `axis`: device tensors by one GPU gather, host tensors through numpy (for the reason _pad_axis1 gives)."""
+    if v.is_cuda:
+        return v.index_select(axis, torch.as_tensor(idx, dtype=torch.int64, device=v.device))
+    return torch.from_numpy(np.ascontiguousarray(np.take(v.numpy(), np.asarray(idx, dtype=np.int64), axis=axis)))
+
+
+def _fit(v, L0, Lk, axis=1, value=0):
+    """Residue axis cut or padded from L0 to Lk."""
+    if Lk == L0:
+        return v
+    if Lk < L0:
+        return v.narrow(axis, 0, Lk).contiguous()
+    if axis == 1:
+        return _pad_axis1(v, Lk - L0, value)
+    lead = tuple(v.shape[:axis - 1])                     # ([2N, B, L0, 20]: fold the leading axis, pad, unfold)
+    w = _pad_axis1(v.reshape((-1,) + tuple(v.shape[axis:])), Lk - L0, value)
+    return w.reshape(lead + tuple(v.shape[axis - 1:axis]) + (Lk,) + tuple(v.shape[axis + 1:]))
+
+
 def fit_cond(cond, L0, Lk, idx=None):
     """The packed conditioning of the samples `idx` (None: all) with the residue axis cut or padded from L0 to Lk by INERT rows: no
     flag set, every class allowed, identity frame, zeros, residue type 21 (none of it is read: padded rows are not generated)."""
     if cond is None:
         return None
-    from .buckets import _fit, _rows
     out = {"partial": cond["partial"]}
     for k in COND_ROW_KEYS:
         v = cond.get(k)
@@ -185,6 +216,16 @@ def fit_cond(cond, L0, Lk, idx=None):
                 w[:, L0:, d, d] = 1
         out[k] = w
     return out
+
+
+def _options(name, given, defaults):
+    """The checks every extension's option dict starts with: a dict, known entries only; -> the entries over their defaults."""
+    if not isinstance(given, dict):
+        raise ValueError(f"{name}: expected None or a dict, got {type(given).__name__}")
+    for k in given:
+        if k not in defaults:
+            raise ValueError(f"{name}: unknown entry {k!r}; the entries are {tuple(defaults)}")
+    return {**defaults, **given}
 
 
 def shard_cond_kwargs(kw, lo, hi, total):
@@ -258,12 +299,7 @@ def make_guide(guide, B, L, generate_mask=None, res_mask=None):
     lo > hi, a negative weight, a power outside {0, 1, 2}, t_on >= 1, more than 64 restraints of one sample."""
     if guide is None:
         return None
-    if not isinstance(guide, dict):
-        raise ValueError(f"guide: expected None or a dict, got {type(guide).__name__}")
-    for k in guide:
-        if k not in GUIDE_DEFAULTS:
-            raise ValueError(f"guide: unknown entry {k!r}; the entries are {tuple(GUIDE_DEFAULTS)}")
-    g = {**GUIDE_DEFAULTS, **guide}
+    g = _options("guide", guide, GUIDE_DEFAULTS)
     gen = None if generate_mask is None else torch.as_tensor(generate_mask).detach().cpu().bool()
     resm = None if res_mask is None else torch.as_tensor(res_mask).detach().cpu().bool()
     vals = {k: float(g[k]) for k in _GUIDE_SLOTS}
@@ -319,7 +355,6 @@ def fit_guide(guide, L0, Lk, idx=None):
     from L0 to Lk (no hot spot on the padding).  Restraints carry residue INDICES: padding is appended at the end, so they stay."""
     if guide is None:
         return None
-    from .buckets import _fit, _rows
     out = dict(guide)
     if guide["hotspots"] is not None:
         h = guide["hotspots"] if idx is None else _rows(guide["hotspots"], idx)
@@ -358,12 +393,7 @@ def make_temper(temper, B, L):
     outside {0, 1, 2}, t_off outside (0, 1], an unknown entry."""
     if temper is None:
         return None
-    if not isinstance(temper, dict):
-        raise ValueError(f"temper: expected None or a dict, got {type(temper).__name__}")
-    for k in temper:
-        if k not in TEMPER_DEFAULTS:
-            raise ValueError(f"temper: unknown entry {k!r}; the entries are {tuple(TEMPER_DEFAULTS)}")
-    t = {**TEMPER_DEFAULTS, **temper}
+    t = _options("temper", temper, TEMPER_DEFAULTS)
     if t["power"] not in (0, 1, 2) or isinstance(t["power"], bool):
         raise ValueError(f"temper['power'] = {t['power']!r}: expected 0, 1 or 2")
     for k in ("sigma_trans", "sigma_rot", "t_off"):
@@ -404,7 +434,6 @@ def fit_temper(temper, L0, Lk, idx=None):
     from L0 to Lk (temperature 1 on the padding: its logits are divided by one and never drawn from)."""
     if temper is None:
         return None
-    from .buckets import _fit, _rows
     out = dict(temper)
     if temper["tau"] is not None:
         p = temper["tau"] if idx is None else _rows(temper["tau"], idx)
@@ -478,15 +507,10 @@ def make_steer(steer, B, L, batch=None, cond=None, guide=None, temper=None):
     members, members that differ (the first differing key and the sample pair are named)."""
     if steer is None:
         return None
-    if not isinstance(steer, dict):
-        raise ValueError(f"steer: expected None or a dict, got {type(steer).__name__}")
-    for k in steer:
-        if k not in STEER_DEFAULTS:
-            raise ValueError(f"steer: unknown entry {k!r}; the entries are {tuple(STEER_DEFAULTS)}")
+    s = _options("steer", steer, STEER_DEFAULTS)
     if guide is None:
         raise ValueError("steer needs guide: the energies the particles are weighted by are the guidance's (guide['scale'] = 0 steers "
                          "without a gradient shift)")
-    s = {**STEER_DEFAULTS, **steer}
     for k in _STEER_SLOTS:
         if isinstance(s[k], bool) or not isinstance(s[k], numbers.Real):
             raise ValueError(f"steer[{k!r}] = {s[k]!r}: expected a number")
@@ -613,10 +637,50 @@ def check_resample_u(noise, steer, num_steps):
                          "(a run on supplied draws is supplied throughout)")
 
 
+@dataclasses.dataclass(frozen=True, eq=False)
+class SampleCall:
+    """What one sample() call has validated and packed on the host: the time grid, the three scalar switches and the packed extensions
+    (None: the call does not use that one).  Made once per call (make), fitted to an engine's padded length or to a length bucket
+    (fit), bound by DeviceSampler.begin."""
+    grid: torch.Tensor
+    flags: tuple = (True, True, True)
+    cond: dict = None
+    guide: dict = None
+    temper: dict = None
+    steer: dict = None
+
+    @classmethod
+    def make(cls, batch, num_steps, sample_bb=True, sample_ang=True, sample_seq=True, *, t_start=None, ts=None, start=None,
+             aa_allowed=None, guide=None, temper=None, steer=None, noise=None):
+        """sample()'s arguments at the caller's [B, L].  The ORDER of the checks is behaviour: a call with two bad arguments raises
+        the first one's error."""
+        B, L = batch["aa"].shape
+        grid, flags, cond = make_cond(B, L, num_steps, sample_bb, sample_ang, sample_seq, t_start, ts, start, aa_allowed)
+        guide = make_guide(guide, B, L, batch.get("generate_mask"), batch.get("res_mask"))
+        temper = make_temper(temper, B, L)
+        check_gauss(noise, temper, int(num_steps), B, L)
+        steer = make_steer(steer, B, L, batch, cond, guide, temper)
+        check_resample_u(noise, steer, int(num_steps))
+        return cls(grid, flags, cond, guide, temper, steer)
+
+    def fit(self, L0, Lk, idx=None):
+        """The call of the samples `idx` (None: all) with the residue axis cut or padded from L0 to Lk (fit_cond / fit_guide / fit_temper
+        / fit_steer)."""
+        return dataclasses.replace(self, cond=fit_cond(self.cond, L0, Lk, idx), guide=fit_guide(self.guide, L0, Lk, idx),
+                                   temper=fit_temper(self.temper, L0, Lk, idx), steer=fit_steer(self.steer, L0, Lk, idx))
+
+    @property
+    def kinds(self):
+        """which extensions the call uses: the keywords of DenoiseEngine.sampler / DeviceSampler"""
+        return {"cond": self.cond is not None, "guide": self.guide is not None, "temper": self.temper is not None,
+                "steer": self.steer is not None}
+
+
 class DeviceSampler:
     """Owned by its engine (DenoiseEngine.sampler caches one per (num_steps, flags, cond, guide, temper, steer)): trajectory buffers and
-    the captured graphs are reused by the next sample() call; set_seed() / set_grid() / set_context() / set_cond() / set_guide() /
-    set_temper() / set_steer() / init_state() are what a call changes."""
+    the captured graphs are reused by the next sample() call.  begin() is what a call changes: the seed, the grid, the context, the
+    packed extensions of its SampleCall (set_cond / set_guide / set_temper / set_steer into buffers this sampler owns) and the
+    initial state."""
 
     def __init__(self, engine, num_steps, flags=(True, True, True), first_sample=0, seed=0, cond=False, guide=False, temper=False,
                  steer=False):
@@ -725,6 +789,40 @@ class DeviceSampler:
         self._graph_key = None
         self._so, self._steps_done = None, 0
         self.set_seed(seed, first_sample)
+
+    @property
+    def precision(self):
+        """the engine's precision mode: what FlowModel's range verdict names (BucketedSampler has the same two members)"""
+        return self.eng.precision
+
+    def operand_range(self):
+        """The engine's report of the largest activations it carried (DenoiseEngine.operand_range)."""
+        return self.eng.operand_range()
+
+    def begin(self, call, native, gen_mask, noise, seed, first_sample=0, sample_ids=None):
+        """The set-up of one call, in this order: seed, grid, sample indices (a length bucket's), context, the extensions of `call` (a
+        SampleCall fitted to this engine's samples and length), initial state.  native = (R1, x1, ang1, seq1) of encode().  Returns
+        the noise the state was initialised from: a steered call's noise["resample_u"] [num_steps, G] cut to the columns of this
+        sampler's groups (call.steer["group_ids"]): a bucket's own groups; on the unbucketed path group_ids = arange(G), so the
+        selection is the identity there (one small host gather per steered call)."""
+        kinds = call.kinds
+        self.set_seed(seed, first_sample)
+        self.set_grid(call.grid)
+        if sample_ids is not None:
+            self.set_sample_ids(sample_ids)
+        self.set_context(*native, gen_mask)
+        if kinds["cond"]:
+            self.set_cond(call.cond, native)
+        if kinds["guide"]:
+            self.set_guide(call.guide)
+        if kinds["temper"]:
+            self.set_temper(call.temper)
+        if kinds["steer"]:
+            self.set_steer(call.steer)
+            if noise.get("resample_u") is not None:
+                noise = {**noise, "resample_u": noise["resample_u"][:, call.steer["group_ids"]].contiguous()}
+        self.init_state(noise)
+        return noise
 
     def set_seed(self, seed, first_sample=0):
         """Philox seed of the in-kernel categorical draws and the global index of this shard's first sample."""
