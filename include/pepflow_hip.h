@@ -1583,6 +1583,56 @@ typedef struct {
 int pf_pack_sidechains_fwd(const pf_pack_args* a, pf_stream_t stream);
 int pf_pack_work_bytes(int B, int N, int max_rot);
 
+/* ---- point-mutation scanning (ABI 65, added entry points) --------------------------------------------------------------------------
+ * pf_mutation_scan_fwd: at every scanned residue (positions set, type in 0..19, N, CA and C present) every rotamer of each candidate
+ * residue type is built on the residue's own backbone and scored as pf_pack_sidechains_fwd scores E_self -- against every other residue
+ * exactly as given (side chains included; neighbours are not repacked), its own residue with the fixed atoms, radii, type bits and
+ * own_mask of the CANDIDATE type, plus rot_energy -- and the best rotamer per type is reported; the conventions are listed in
+ * csrc/mutscan.hip.  energy[q,t] - energy[q,aa[q]] is what an alanine scan (t = ALA) or a position scan reports.  It is NOT FoldX and
+ * NOT Rosetta (no solvation, electrostatics, entropy or backbone movement; untuned): it takes their place in role only.  Tables,
+ * rotamer table, cutoff, weights, pro and cys as pf_pack_args; candidates [B,N,20] optional (null: all; the wild type is always
+ * evaluated); group [B,N] optional.
+ *   scanned [B,N]; energy [B,N,20] (+inf where not evaluated) with the bits of pf_pack_sidechains_fwd's energy_self_best on the input
+ *   with aa[q] := t and q alone movable; rotamer [B,N,20] (-1); n_rotamers [B,N,20] (0); chi [B,N,20,4] (the chosen row; 0);
+ *   energy_interface [B,N,20] (+inf): the chosen rotamer's terms against residues of another group byte (0 without group).
+ * work: pf_mutation_scan_work_bytes(B, N) bytes (272 per residue: nothing per type or rotamer), 16-byte aligned, no initialisation
+ * needed (-1: N > PF_PACK_MAX_N, a negative size, or more than INT_MAX bytes).  Two launches, no atomics, one writer per output, every
+ * sum in packing's order: bit-identical from run to run and independent of the rest of the batch, of the other positions and of the
+ * other candidates; the host reads nothing back.  N > PF_PACK_MAX_N, max_rot > PF_PACK_MAX_ROT or B > 65535 -> PF_E_TOOLARGE. */
+#define PF_MUTATION_SCAN_TYPES 20
+typedef struct {
+    const float* pos;                                               /* [B,N,n_atoms,3] */
+    const unsigned char* atom_mask;                                 /* [B,N,n_atoms] */
+    const int64_t* aa;                                              /* [B,N] */
+    const int* residue_index;                                       /* [B,N] */
+    const unsigned char* positions;                                 /* [B,N] */
+    const unsigned char* candidates;                                /* [B,N,20] optional */
+    const unsigned char* group;                                     /* [B,N] optional */
+    const float* radius;                                            /* [21,15] as pf_pack_args, down to rot_energy */
+    const unsigned char* types;                                     /* [21,15] */
+    const int* own_mask;                                            /* [21,15] */
+    const float* tab_rot;                                           /* [21,8,9] */
+    const float* tab_trans;                                         /* [21,8,3] */
+    const int* tab_group;                                           /* [21,14] */
+    const float* tab_pos;                                           /* [21,14,3] */
+    const unsigned char* tab_mask;                                  /* [22,15] */
+    const float* rot_chi;                                           /* [21,max_rot,4] radians */
+    const int* rot_count;                                           /* [21] */
+    const float* rot_energy;                                        /* [21,max_rot] */
+    void* work;                                                     /* pf_mutation_scan_work_bytes(B, N) bytes */
+    unsigned char* scanned;                                         /* [B,N] */
+    float* energy;                                                  /* [B,N,20] */
+    int* rotamer;                                                   /* [B,N,20] */
+    int* n_rotamers;                                                /* [B,N,20] */
+    float* chi;                                                     /* [B,N,20,4] */
+    float* energy_interface;                                        /* [B,N,20] */
+    int B, N, n_atoms, max_rot, pro, cys;
+    float cutoff;                                                   /* > 0; 8.0 */
+    float w_gauss1, w_gauss2, w_repulsion, w_hydrophobic, w_hbond;  /* -0.0356, -0.00516, 0.840, -0.0351, -0.587 */
+} pf_mutation_scan_args;
+int pf_mutation_scan_fwd(const pf_mutation_scan_args* a, pf_stream_t stream);
+int pf_mutation_scan_work_bytes(int B, int N);
+
 /* ---- empirical interface energy (ABI 64, added entry point) -----------------------------------------------------------------------
  * pf_interface_energy_fwd: the functional form of AutoDock Vina's scoring function (Trott & Olson, J. Comput. Chem. 2010) over the
  * heavy atoms of a batch of structures, between atoms of residues whose group bytes differ; the conventions are listed in

@@ -305,6 +305,16 @@ class PackArgs(C.Structure):
                 ("w_hydrophobic", C.c_float), ("w_hbond", C.c_float)]
 
 
+class MutationScanArgs(C.Structure):
+    _fields_ = [("pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("residue_index", _fp), ("positions", _fp), ("candidates", _fp),
+                ("group", _fp), ("radius", _fp), ("types", _fp), ("own_mask", _fp), ("tab_rot", _fp), ("tab_trans", _fp),
+                ("tab_group", _fp), ("tab_pos", _fp), ("tab_mask", _fp), ("rot_chi", _fp), ("rot_count", _fp), ("rot_energy", _fp),
+                ("work", _fp), ("scanned", _fp), ("energy", _fp), ("rotamer", _fp), ("n_rotamers", _fp), ("chi", _fp),
+                ("energy_interface", _fp), ("B", _i), ("N", _i), ("n_atoms", _i), ("max_rot", _i), ("pro", _i), ("cys", _i),
+                ("cutoff", C.c_float), ("w_gauss1", C.c_float), ("w_gauss2", C.c_float), ("w_repulsion", C.c_float),
+                ("w_hydrophobic", C.c_float), ("w_hbond", C.c_float)]
+
+
 class InterfaceEnergyArgs(C.Structure):
     _fields_ = [("pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("group", _fp), ("query", _fp), ("radius", _fp), ("types", _fp),
                 ("work", _fp), ("terms_atom", _fp), ("terms_residue", _fp), ("energy_residue", _fp), ("pairs_atom", _fp),
@@ -428,6 +438,8 @@ _SIGNATURES = {
     "pf_cluster_work_bytes": ([_i, _i], _i),
     "pf_pack_sidechains_fwd": ([C.POINTER(PackArgs), _fp], _i),
     "pf_pack_work_bytes": ([_i, _i, _i], _i),
+    "pf_mutation_scan_fwd": ([C.POINTER(MutationScanArgs), _fp], _i),
+    "pf_mutation_scan_work_bytes": ([_i, _i], _i),
     "pf_interface_energy_fwd": ([C.POINTER(InterfaceEnergyArgs), _fp], _i),
     "pf_relax_energy_fwd": ([C.POINTER(RelaxArgs), _fp], _i),
     "pf_relax_fwd": ([C.POINTER(RelaxArgs), _fp], _i),

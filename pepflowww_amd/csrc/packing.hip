@@ -63,21 +63,14 @@
 //   search_kernel  one workgroup per sample.  The current rotamer atoms of its packed residues stay in LDS when there are at most 96
 //                  of them, else they are read from the workspace.  The sweep loop, argmins, stop test, trace, totals and the output
 //                  structure are all done here.  A pair of residues is looked at when their CAs are within (E + E' + cutoff).
-#include "common.h"
-#include "../../include/pepflow_hip.h"
-#include "eval_dev.h"
+#include "pack_dev.h"
 
 namespace {
 
-constexpr int SL = PF_PACK_SLOTS, RA = PF_PACK_ROT_ATOMS, S0 = 5;      // slots per residue, rotamer atoms per residue, their first slot
-constexpr int MAXR = PF_PACK_MAX_ROT, MAXN = PF_PACK_MAX_N;
-constexpr int TR = 16, TA = TR * SL, NT = 256;                          // environment tile: residues, atoms; threads
+using namespace pack_dev;
+
 constexpr int RT = 28, ROWS = RT * RA;                                  // rotamers and rows per workgroup of self_kernel
-constexpr int MAX_TILES = MAXN / TR;
 constexpr int LDS_RES = 96;                                             // packed residues whose current atoms fit in LDS
-constexpr float FAR = 1e18f;
-constexpr float CULL_SLACK = 1.0001f, CULL_ABS = 1e-3f;
-constexpr unsigned char HYDROPHOBIC = 1, DONOR = 2, ACCEPTOR = 4, IS_SG = 8;
 
 struct Work {
     float4* env;                    // [B,N,15]
@@ -102,57 +95,6 @@ __host__ __device__ inline Work carve(void* work, size_t rows, int R) {
 
 constexpr long long BYTES_FIXED = SL * 16 + 16 + 16 + 16, BYTES_PER_ROT = RA * 16 + 4;     // per residue; per residue and rotamer
 
-__device__ __forceinline__ float dist3(const float4& p, const float4& q) {
-    const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-    return sqrtf((dx * dx + dy * dy) + dz * dz);
-}
-
-// the pair function of interface_energy.hip's energy_kernel: adds the pair (P, v) to the five sums when it is inside the cutoff
-__device__ __forceinline__ void pair_add(const float4& P, unsigned char fp, const float4& v, unsigned char fv, float cut2, float t[5]) {
-    const float dx = P.x - v.x, dy = P.y - v.y, dz = P.z - v.z;
-    const float r2 = (dx * dx + dy * dy) + dz * dz;
-    if (r2 < cut2) {
-        const float d = sqrtf(r2) - (P.w + v.w);
-        const float g1 = d * 2.f, g2 = (d - 3.f) * 0.5f;
-        t[0] += expf(-(g1 * g1));
-        t[1] += expf(-(g2 * g2));
-        t[2] += d < 0.f ? d * d : 0.f;
-        const bool hp = (fp & HYDROPHOBIC) && (fv & HYDROPHOBIC);
-        const bool hb = ((fp & DONOR) && (fv & ACCEPTOR)) || ((fp & ACCEPTOR) && (fv & DONOR));
-        t[3] += !hp ? 0.f : d <= 0.5f ? 1.f : d >= 1.5f ? 0.f : 1.5f - d;
-        t[4] += !hb ? 0.f : d <= -0.7f ? 1.f : d >= 0.f ? 0.f : d * (-1.f / 0.7f);
-    }
-}
-
-__device__ __forceinline__ float weighted(const pf_pack_args& a, const float t[5]) {
-    return (((a.w_gauss1 * t[0] + a.w_gauss2 * t[1]) + a.w_repulsion * t[2]) + a.w_hydrophobic * t[3]) + a.w_hbond * t[4];
-}
-
-__device__ __forceinline__ int rot_count(const pf_pack_args& a, int t) {
-    const int c = a.rot_count[t];
-    return c < 1 ? 1 : c > a.max_rot ? a.max_rot : c;
-}
-
-// (value, index) total order of the argmins; NaN was mapped to +inf by the caller
-__device__ __forceinline__ bool better(float v, int i, float v2, int i2) { return v < v2 || (v == v2 && i < i2); }
-
-__device__ __forceinline__ float no_nan(float v) { return v == v ? v : INFINITY; }
-
-__device__ __forceinline__ void apply(const float R[9], const float t[3], const float q[3], float o[3]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = R[i * 3] * q[0] + R[i * 3 + 1] * q[1] + R[i * 3 + 2] * q[2] + t[i];
-}
-
-// (R, t) = (R1, t1) o (R2, t2), as full_atom.hip composes
-__device__ __forceinline__ void compose(const float* R1, const float* t1, const float* R2, const float* t2, float* R, float* t) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) R[i * 3 + j] = R1[i * 3] * R2[j] + R1[i * 3 + 1] * R2[3 + j] + R1[i * 3 + 2] * R2[6 + j];
-        t[i] = R1[i * 3] * t2[0] + R1[i * 3 + 1] * t2[1] + R1[i * 3 + 2] * t2[2] + t1[i];
-    }
-}
-
 __global__ __launch_bounds__(MAXR) void build_kernel(pf_pack_args a, Work w) {
     __shared__ float wave_max[MAXR / 64];
     const int q = blockIdx.x, tid = threadIdx.x, A = a.n_atoms, R = a.max_rot;
@@ -163,125 +105,32 @@ __global__ __launch_bounds__(MAXR) void build_kernel(pf_pack_args a, Work w) {
     const float* p = a.pos + i * A * 3;
     const bool pk = a.movable[i] != 0 && aa >= 0 && aa <= 19 && m[0] != 0 && m[1] != 0 && m[2] != 0;
 
-    float Rb[9], tb[3] = {0.f, 0.f, 0.f}, cb[3] = {0.f, 0.f, 0.f}, chi1_eps = 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Rb[k] = 0.f;
-    if (pk) {                                               // construct_3d_basis(CA, C, N)
-        float u[3], v[3], e1[3], e2[3], e3[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            tb[k] = p[3 + k];
-            u[k] = p[6 + k] - p[3 + k];
-            v[k] = p[k] - p[3 + k];
-        }
-        const float lu = sqrtf((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]) + 1e-6f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) e1[k] = u[k] / lu;
-        const float pr = (e1[0] * v[0] + e1[1] * v[1]) + e1[2] * v[2];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v[k] = v[k] - pr * e1[k];
-        const float lv = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + 1e-6f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) e2[k] = v[k] / lv;
-        e3[0] = e1[1] * e2[2] - e1[2] * e2[1];
-        e3[1] = e1[2] * e2[0] - e1[0] * e2[2];
-        e3[2] = e1[0] * e2[1] - e1[1] * e2[0];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            Rb[k * 3] = e1[k];
-            Rb[k * 3 + 1] = e2[k];
-            Rb[k * 3 + 2] = e3[k];
-        }
-        apply(Rb, tb, a.tab_pos + ((size_t)t * 14 + 4) * 3, cb);
-        // chi1 is the dihedral N-CA-CB-CG from the REAL N; the chain turns from where the ideal N is.  In the backbone frame both lie
-        // in the e1-e2 plane; eps = the signed angle about CA-CB from the real N's projection to the ideal N's.
-        if (a.tab_mask[t * SL + 4]) {
-            const float* q = a.tab_pos + ((size_t)t * 14 + 4) * 3;
-            const float* ni = a.tab_pos + (size_t)t * 14 * 3;
-            const float nr[3] = {pr, (e2[0] * v[0] + e2[1] * v[1]) + e2[2] * v[2], 0.f};
-            const float lq = sqrtf((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]);
-            if (lq > 0.f) {
-                const float ax[3] = {q[0] / lq, q[1] / lq, q[2] / lq};
-                const float dr = (nr[0] * ax[0] + nr[1] * ax[1]) + nr[2] * ax[2], di = (ni[0] * ax[0] + ni[1] * ax[1]) + ni[2] * ax[2];
-                const float pa[3] = {nr[0] - dr * ax[0], nr[1] - dr * ax[1], nr[2] - dr * ax[2]};
-                const float pb[3] = {ni[0] - di * ax[0], ni[1] - di * ax[1], ni[2] - di * ax[2]};
-                const float cx[3] = {pa[1] * pb[2] - pa[2] * pb[1], pa[2] * pb[0] - pa[0] * pb[2], pa[0] * pb[1] - pa[1] * pb[0]};
-                const float y = (ax[0] * cx[0] + ax[1] * cx[1]) + ax[2] * cx[2], x = (pa[0] * pb[0] + pa[1] * pb[1]) + pa[2] * pb[2];
-                const float e = atan2f(y, x);
-                if (e == e) chi1_eps = e;
-            }
-        }
-    }
+    Backbone F;
+    backbone_frame(a, t, p, pk, F);
 
     if (tid == 0) {                                         // the environment atoms of this residue and their bounds
         float4 e[SL];
+        unsigned char flg[SL];
+        env_atoms(a, t, m, p, A, pk, F.cb, e, flg);
         for (int s = 0; s < SL; ++s) {
-            const float rad = a.radius[t * SL + s];
-            const bool input = s < A && m[s] != 0 && rad > 0.f;
-            e[s] = make_float4(-FAR, 0.f, 0.f, 0.f);
-            if (pk && s == 4) {
-                if (a.tab_mask[t * SL + 4] && rad > 0.f) e[s] = make_float4(cb[0], cb[1], cb[2], rad);
-            } else if (input && (!pk || s < 4 || s == 14)) {
-                e[s] = make_float4(p[3 * s], p[3 * s + 1], p[3 * s + 2], rad);
-            }
             w.env[i * SL + s] = e[s];
-            w.envflg[i * 16 + s] = (unsigned char)(a.types[t * SL + s] | (t == a.cys && s == S0 ? IS_SG : 0));
+            w.envflg[i * 16 + s] = flg[s];
         }
         w.envflg[i * 16 + 15] = 0;
-        int c = e[1].w > 0.f ? 1 : -1;
-        for (int s = 0; s < SL && c < 0; ++s)
-            if (e[s].w > 0.f) c = s;
-        float4 bd = make_float4(0.f, 0.f, 0.f, -1.f);
-        if (c >= 0) {
-            bd = make_float4(e[c].x, e[c].y, e[c].z, 0.f);
-            for (int s = 0; s < SL; ++s)
-                if (e[s].w > 0.f) bd.w = fmaxf(bd.w, dist3(e[s], bd));
-        }
-        w.ebound[i] = bd;
+        w.ebound[i] = env_bound(e);
     }
 
     float ext = 0.f;
     if (pk && tid < rot_count(a, t)) {
-        const float* chi = a.rot_chi + ((size_t)t * R + tid) * 4;
-        float Rc[9], tc[3];                                 // the current frame: the backbone's, then chi1 .. chi4
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Rc[k] = Rb[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) tc[k] = tb[k];
-        const float zero3[3] = {0.f, 0.f, 0.f};
-        const float4 ca = make_float4(tb[0], tb[1], tb[2], 0.f);
         float4* dst = w.rot + (i * R + tid) * RA;
         for (int j = 0; j < RA; ++j) dst[j] = make_float4(FAR, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const float ang = f == 0 ? chi[0] - chi1_eps : chi[f];
-            const float sn = sinf(ang), cs = cosf(ang);
-            const float Rx[9] = {1.f, 0.f, 0.f, 0.f, cs, -sn, 0.f, sn, cs};
-            const float* Rg = a.tab_rot + ((size_t)t * 8 + 4 + f) * 9;
-            const float* tg = a.tab_trans + ((size_t)t * 8 + 4 + f) * 3;
-            float Rm[9], tm[3], Rn[9], tn[3];
-            compose(Rg, tg, Rx, zero3, Rm, tm);
-            compose(Rc, tc, Rm, tm, Rn, tn);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) Rc[k] = Rn[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) tc[k] = tn[k];
-            for (int j = 0; j < RA; ++j) {                  // the atoms of this frame's rigid group
-                const int s = S0 + j;
-                if (a.tab_group[t * 14 + s] != 4 + f || !a.tab_mask[t * SL + s]) continue;
-                float x[3];
-                apply(Rc, tc, a.tab_pos + ((size_t)t * 14 + s) * 3, x);
-                const float4 o = make_float4(x[0], x[1], x[2], a.radius[t * SL + s]);
-                ext = fmaxf(ext, dist3(o, ca));
-                dst[j] = o;
-            }
-        }
+        ext = build_rotamer(a, t, a.rot_chi + ((size_t)t * R + tid) * 4, F, [dst](int j, const float4& o) { dst[j] = o; });
     }
 #pragma unroll
     for (int k = 32; k >= 1; k >>= 1) ext = fmaxf(ext, __shfl_xor(ext, k));
     if ((tid & 63) == 0) wave_max[tid >> 6] = ext;
     __syncthreads();
-    if (tid == 0) w.rbound[i] = make_float4(tb[0], tb[1], tb[2], pk ? fmaxf(wave_max[0], wave_max[1]) : -1.f);
+    if (tid == 0) w.rbound[i] = make_float4(F.t[0], F.t[1], F.t[2], pk ? fmaxf(wave_max[0], wave_max[1]) : -1.f);
 }
 
 struct Tile {
@@ -347,14 +196,7 @@ __global__ __launch_bounds__(NT) void self_kernel(pf_pack_args a, Work w) {
     const long long my_idx = a.residue_index[i];
 
     if (tid < 64) {                                         // the column tiles to visit, ascending: wave 0, a tile per lane
-        bool keep = false;
-        if (tid < n_tiles) {
-            const int q1 = tid * TR + TR < N ? tid * TR + TR : N;
-            for (int c = tid * TR; c < q1; ++c) {
-                const float4 e = ebound[c];
-                keep = keep || (e.w >= 0.f && dist3(e, C) <= ((C.w + e.w) + cutoff) * CULL_SLACK + CULL_ABS);
-            }
-        }
+        const bool keep = tid < n_tiles && tile_near(ebound, tid * TR, tid * TR + TR < N ? tid * TR + TR : N, C, cutoff);
         const unsigned long long bal = __ballot(keep);
         if (keep) list[__popcll(bal & ((1ull << tid) - 1ull))] = tid;
         if (tid == 0) n_list = __popcll(bal);

@@ -5,7 +5,7 @@ Input families, one binding path each:
   pair work lists   point sets x [Bx,N,3] / y [By,N,3] with masks and `pairs` [P,2] -- `_pair_inputs`: superpose (and align, batch_align,
                     superpose_rmsd), tm_score, tm_align and their pairwise_* matrices (`_within_groups`, `_mirrored`);
   heavy-atom structures   pos [B,N,A,3], atom_mask [B,N,A] and per-residue [B,N] tensors -- `_structure`: structural_violations, sasa,
-                    torsion_angles, interface_energy, polar_interactions and each side of sidechain_compare (dssp reads the same pos with a residue mask);
+                    torsion_angles, interface_energy, polar_interactions, pack_sidechains, mutation_scan and each side of sidechain_compare (dssp reads the same pos with a residue mask);
                     cavity_scan (pf_cavity_fwd: buriedness scan, cavities and lining residues of whole receptors, N <= 4096) too;
   both at once      two heavy-atom structure sets and a work list -- `_structure_pairs`: lddt (pf_lddt_fwd, the values of OpenFold's
                     lddt / lddt_ca, openfold/utils/loss.py:382-458) and interface_contacts (pf_contacts_fwd), which dockq combines
@@ -1587,6 +1587,99 @@ def pack_sidechains(pos, atom_mask, aa, residue_index, movable, rotamers=None, s
         a.w_gauss1, a.w_gauss2, a.w_repulsion, a.w_hydrophobic, a.w_hbond = w
         _capi.check(lib.pf_pack_sidechains_fwd(C.byref(a), _capi.stream_ptr()), "pf_pack_sidechains_fwd")
     _as_bool(out, "atom_mask", "packed")
+    return out
+
+
+# Point-mutation scanning (conventions: csrc/mutscan.hip).  It is NOT FoldX (which the reference's eval/foldx.py calls; its main uses
+# are AlaScan and PositionScan) and NOT Rosetta: the energy is `pack_sidechains`' E_self on an unmoved, unrepacked environment.
+SCAN_TYPES = 20             # PF_MUTATION_SCAN_TYPES: the candidate residue types 0..19
+
+
+def _scan_candidates(candidates, B, N):
+    """None (every type), a [20] mask or a [B,N,20] mask -> None or a [B,N,20] bool tensor (ValueError)"""
+    if candidates is None:
+        return None
+    c = torch.as_tensor(candidates)
+    if tuple(c.shape) == (SCAN_TYPES,):
+        c = c.reshape(1, 1, SCAN_TYPES).expand(B, N, SCAN_TYPES)
+    if tuple(c.shape) != (B, N, SCAN_TYPES):
+        raise ValueError(f"candidates must be None, [{SCAN_TYPES}] or [B,N,{SCAN_TYPES}] = {(B, N, SCAN_TYPES)}, got {tuple(c.shape)}")
+    return c != 0
+
+
+def mutation_scan(pos, atom_mask, aa, residue_index, positions, candidates=None, group=None, rotamers=None, cutoff=8.0,
+                  weights=VINA_WEIGHTS):
+    """pf_mutation_scan_fwd: single-point mutants of the residues `positions` on the device (conventions: csrc/mutscan.hip).  At each
+    scanned residue q and for each candidate type t, every rotamer of t is built on q's own backbone as `pack_sidechains` builds it
+    and scored with its E_self: against every other residue exactly as given (side chains included; neighbours are not repacked and
+    other scanned positions stay as they are), against the own residue with type t's atoms, and the table's energy; the smallest is
+    kept.  ddE[q,t] = energy[q,t] - energy[q,aa[q]]: the wild type is repacked on the same rotamer grid, so ddE is exactly 0 at t =
+    aa[q].  energy[q,t] has the bits of `pack_sidechains(aa with aa[q] := t, movable = onehot(q), sweeps=0)["energy_self_best"][q]`.
+
+    What the numbers are, and are not: ALA and GLY have no rotamer atom, so both score the table's energy (0 by default), and
+    ddE[q,ALA] is minus the contribution of q's side chain beyond CB, which is what an alanine scan reports; differences in the
+    backbone (PRO's N, GLY's missing CB) do not show; there is no solvation, no electrostatics, no entropy and no backbone movement.
+    It is NOT FoldX and NOT Rosetta, and it stands for their AlaScan / PositionScan in role only; the defaults are untuned.
+
+    Arguments as `pack_sidechains` with positions [B,N] in place of movable: a residue is scanned where positions is set, its type is
+    in 0..19 and its N, CA and C are in atom_mask.  candidates: None (all 20 types), a [20] mask or a [B,N,20] mask; the wild type is
+    evaluated at every scanned residue whatever the mask says.  group [B,N] (optional): energy_interface counts only partners whose
+    group differs from the residue's.  rotamers, cutoff, weights as `pack_sidechains`.
+    -> dict of device tensors: scanned [B,N] bool; energy [B,N,20] float32 (+inf where not evaluated); rotamer [B,N,20] int32 (-1);
+    n_rotamers [B,N,20] int32 (0); chi [B,N,20,4] float32 (the chosen row); energy_interface [B,N,20] float32 (the chosen rotamer's
+    pair terms against residues of another group; 0 without group, +inf where not evaluated); ddE and ddE_interface [B,N,20] float32
+    (NaN where either side is not evaluated)."""
+    if positions is None or residue_index is None:
+        raise ValueError("mutation_scan needs residue_index [B,N] and positions [B,N]")
+    cutoff, w = _positive("cutoff", cutoff), _weights(weights)
+    rot = None if rotamers is None else _check_rotamers(rotamers)
+    dev, (B, N, A), pos, atom_mask, (aa, residue_index, positions, group) = _structure(pos, atom_mask, (
+        ("aa", aa, torch.int64), ("residue_index", residue_index, torch.int32), ("positions", positions, torch.uint8),
+        ("group", group, torch.uint8)), max_n=PACK_MAX_N)
+    cand = _scan_candidates(candidates, B, N)
+    cand = None if cand is None else _bytes(cand, dev)
+    T = SCAN_TYPES
+    out = {"scanned": torch.zeros(B, N, dtype=torch.uint8, device=dev), "energy": torch.full((B, N, T), float("inf"), device=dev),
+           "rotamer": torch.full((B, N, T), -1, dtype=torch.int32, device=dev),
+           "n_rotamers": torch.zeros(B, N, T, dtype=torch.int32, device=dev), "chi": torch.zeros(B, N, T, 4, device=dev),
+           "energy_interface": torch.full((B, N, T), float("inf"), device=dev)}
+    if B and N:
+        from . import full_atom
+        if rot is None:
+            tabs = [_table("rotamer_" + k, dev, lambda k=k: dict(zip(("chi", "count", "energy"), rotamer_table()))[k])
+                    for k in ("chi", "count", "energy")]
+        else:
+            tabs = [t.to(dev) for t in rot]
+        R = tabs[0].shape[1]
+        rigid, frames = full_atom._tables(dev)
+        if frames != [3, 4, 5, 6, 7]:
+            raise _capi.PepflowHipError(f"rigid_groups.npz: the frames are {frames}, the scan kernel is written for [3, 4, 5, 6, 7]")
+        lib = _capi.load()
+        nbytes = lib.pf_mutation_scan_work_bytes(B, N)
+        if nbytes < 0:
+            raise ValueError(f"mutation_scan: the workspace for B = {B}, N = {N} exceeds 2 GiB; scan the batch in parts")
+        a = _capi.MutationScanArgs()
+        _bind_in(a, pos=pos, atom_mask=atom_mask, aa=aa, residue_index=residue_index, positions=positions, candidates=cand, group=group)
+        a.radius = _table("xs_radius", dev, xs_radius_table).data_ptr()
+        a.types = _table("interface_types", dev, interface_type_table).data_ptr()
+        a.own_mask = _table("pack_own_mask", dev, _pack_own_mask_table).data_ptr()
+        a.tab_rot, a.tab_trans, a.tab_group, a.tab_pos, a.tab_mask = (rigid[k].data_ptr() for k in ("rot", "trans", "group", "pos", "mask"))
+        a.rot_chi, a.rot_count, a.rot_energy = (t.data_ptr() for t in tabs)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        a.work = work.data_ptr()
+        _bind_out(a, out)
+        a.B, a.N, a.n_atoms, a.max_rot, a.pro, a.cys = B, N, A, R, _proline(), _cysteine()
+        a.cutoff = cutoff
+        a.w_gauss1, a.w_gauss2, a.w_repulsion, a.w_hydrophobic, a.w_hbond = w
+        _capi.check(lib.pf_mutation_scan_fwd(C.byref(a), _capi.stream_ptr()), "pf_mutation_scan_fwd")
+    _as_bool(out, "scanned")
+    # ddE on the device: against the wild type's own entry; NaN where either side was not evaluated
+    done = out["rotamer"] >= 0
+    wt = aa.clamp(0, T - 1)[:, :, None]
+    ok = done & torch.gather(done, 2, wt)
+    nan = torch.full((), float("nan"), device=dev)
+    for k, src in (("ddE", "energy"), ("ddE_interface", "energy_interface")):
+        out[k] = torch.where(ok, out[src] - torch.gather(out[src], 2, wt), nan)
     return out
 
 

@@ -16,10 +16,12 @@ complex, their representatives and the best-scored member of each (`cluster_samp
 follows the publication and is not checked against GROMACS, and single / complete / average linkage cut at a height, checked against
 scipy's fcluster(criterion="distance") as partitions only); rotamer side chains for a backbone-only sample, a staggered rotamer grid
 scored with the interface energy's pair function and chosen by iterated conditional modes, which is not SCWRL4 and not Rosetta's
-packer and takes their place in role only (`pack_samples`, and backbone="packed" in the structure metrics).
+packer and takes their place in role only (`pack_samples`, and backbone="packed" in the structure metrics); point-mutation scanning of
+the generated residues, an alanine scan and a position scan with the packer's self energy on an unmoved environment, which is not FoldX
+(eval/foldx.py) and not Rosetta and takes their place in role only (`mutation_scan`).
 
 Every per-residue, per-point and per-atom-pair operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd /
-pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_polar_fwd / pf_relax_fwd / pf_cluster_fwd / pf_pack_sidechains_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
+pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_polar_fwd / pf_relax_fwd / pf_cluster_fwd / pf_pack_sidechains_fwd / pf_mutation_scan_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
@@ -720,4 +722,75 @@ def pack_samples(final, batch, backbone="frames", **kw):
     out["chi_mae"] = (c["err_sum"] * deg / cnt)[:, 4:]
     out["chi_correct"] = (c["within"].double() / cnt)[:, 4:]
     out["residue_correct"] = c["res_correct"].double() / c["res_with_chi"].double()
+    return out
+
+
+HOT_SPOT_DDE = 1.0          # ddE_ala at or above which a residue is called a hot spot: a starting value in this energy's units, not tuned
+
+
+def _scan_candidate_mask(candidates):
+    """"all" | "ALA" | a sequence of three-letter residue names -> None (every type) or a [20] bool mask (ValueError)"""
+    from .preprocess import residue_type
+    if isinstance(candidates, str):
+        if candidates == "all":
+            return None
+        candidates = (candidates,)
+    try:
+        names = list(candidates)
+    except TypeError:
+        raise ValueError(f"candidates must be 'all', 'ALA' or a sequence of residue names, got {candidates!r}") from None
+    mask = torch.zeros(geometry.SCAN_TYPES, dtype=torch.bool)
+    for n in names:
+        t = residue_type(n) if isinstance(n, str) else None
+        if t is None or not 0 <= t < geometry.SCAN_TYPES:
+            raise ValueError(f"candidates: {n!r} is not one of the 20 residue types")
+        mask[t] = True
+    if not names:
+        raise ValueError("candidates names no residue type")
+    return mask
+
+
+def mutation_scan(final, batch, backbone="packed", candidates="all", hot_spot=HOT_SPOT_DDE, top_k=5, **kw):
+    """Point-mutation scanning of each sample's generated residues against the complex as it stands, on the device (geometry.
+    mutation_scan: at every generated residue and for every candidate type, the best rotamer's self energy of `pack_sidechains` with
+    nothing else moved or repacked, minus the wild type's on the same rotamer grid).  It answers which residues carry the binding (an
+    alanine scan: ddE_ala) and which single substitutions would score better (a position scan: ddE, top_*), where the reference's
+    evaluation calls FoldX's AlaScan / PositionScan (eval/foldx.py) or Rosetta.  It is NOT FoldX and NOT Rosetta and takes their
+    place in role only: this package's Vina-form pair energy, no solvation, no electrostatics, no entropy, no backbone movement;
+    ALA and GLY both score 0 and differences in the backbone (PRO's N, GLY's missing CB) do not show; the defaults are untuned.
+    final / batch and the sample's complex are those of `binding_energy` (`_complexes`; the default backbone "packed" places the
+    side chains first, "frames" scans a backbone-only peptide); positions = generate_mask & res_mask, group = the same mask (so
+    *_interface is the part against the receptor), the index comes from `residue_index`, the types are where(generate, seqs, seqs_1).
+    candidates: "all", "ALA" or a sequence of three-letter names (the wild type is evaluated besides); hot_spot: the ddE_ala at or
+    above which a residue is called a hot spot -- HOT_SPOT_DDE is a starting value, not a tuned one; kw (rotamers, cutoff, weights)
+    goes to geometry.mutation_scan.
+
+    -> dict of device tensors: ddE, ddE_interface [B,L,20] float32 (NaN where not evaluated; 0 at the wild type); energy [B,L,20]
+    and rotamer [B,L,20] as geometry.mutation_scan gives them; scanned [B,L] bool; ddE_ala [B,L] = ddE[..., ALA]; hot_spot [B,L] bool
+    (ddE_ala >= hot_spot); top_position, top_type [B,top_k] int64 and top_ddE [B,top_k] float32: the top_k most favourable
+    substitutions of each sample other than the wild type, ascending in ddE (torch.topk; where a sample has fewer candidates the
+    rest are position -1, type -1, ddE NaN)."""
+    from .preprocess import residue_type
+    _check_backbone(backbone)
+    cand = _scan_candidate_mask(candidates)
+    if not isinstance(top_k, int) or isinstance(top_k, bool) or top_k < 0:
+        raise ValueError(f"top_k must be an integer >= 0, got {top_k!r}")
+    hot_spot = float(hot_spot)
+    if math.isnan(hot_spot):
+        raise ValueError("hot_spot must be a number")
+    dev, res_mask, gen, index, (pos, mask, aa), _ = _complexes(final, batch, backbone, index=True)
+    r = geometry.mutation_scan(pos, mask & res_mask[:, :, None], aa, index, gen, candidates=cand, group=gen, **kw)
+    B, L, T = r["ddE"].shape
+    ala = residue_type("ALA")
+    out = {"ddE": r["ddE"], "ddE_interface": r["ddE_interface"], "energy": r["energy"], "rotamer": r["rotamer"], "scanned": r["scanned"],
+           "ddE_ala": r["ddE"][:, :, ala]}
+    out["hot_spot"] = out["ddE_ala"] >= hot_spot
+    wild = torch.arange(T, device=dev)[None, None, :] == aa[:, :, None]
+    score = torch.where(torch.isnan(r["ddE"]) | wild, torch.full((), float("inf"), device=dev), r["ddE"]).reshape(B, L * T)
+    k = min(top_k, L * T)
+    v, at = torch.topk(score, k, dim=1, largest=False, sorted=True)
+    found = torch.isfinite(v)
+    out["top_position"] = torch.where(found, torch.div(at, T, rounding_mode="floor"), torch.full_like(at, -1))
+    out["top_type"] = torch.where(found, at % T, torch.full_like(at, -1))
+    out["top_ddE"] = torch.where(found, v, torch.full_like(v, float("nan")))
     return out
