@@ -1427,6 +1427,72 @@ typedef struct {
 } pf_polar_args;
 int pf_polar_fwd(const pf_polar_args* a, pf_stream_t stream);
 
+/* ---- sequence ratio, pairwise alignment and library search (ABI 65, added entry points) ---------------------------------------------
+ * Sequence comparison of peptides of different lengths; the conventions are listed in csrc/seqalign.hip.  The first two take the
+ * pair-work-list family of pf_superpose_fwd on residue types: the sequence of side x in pair p = (i, j) is aa_x[i] where mx[i] is set, in
+ * order (compacted on the device, N is not bounded), side y likewise from aa_y[j], my[j]; a type outside 0..19 is 20 ("X").  A compacted
+ * length above PF_SEQ_MAX_LEN on either side, or a pair index out of range, writes the fill values.  One launch each, no atomics, no
+ * scratch, one writer per output, integers but for one float64 division per pair: bit-identical from run to run and independent of the
+ * rest of the list.  Every loop of the kernels has a constant trip bound or runs over a size argument.
+ *
+ * pf_seq_ratio_fwd: difflib.SequenceMatcher(None, x, y) -- matches (the sum of the matching blocks), total = len x + len y and
+ * ratio = 2.0 * matches / total in float64 (1.0 when total is 0), the values of the reference's diff_ratio (eval/geometry.py); blocks
+ * [P,64,3] / n_blocks [P] (optional, both or neither): get_matching_blocks() without its sentinel, unused rows (-1, -1, 0).
+ * Fill: ratio NaN, matches, total, n_blocks -1.
+ *
+ * pf_seq_align_fwd: Gotoh's affine-gap alignment in int32 with matrix [21,21] (int8); a gap of length g costs
+ * gap_open + (g - 1) gap_extend, 0 <= gap_extend <= gap_open <= PF_SEQ_MAX_GAP.  PF_SEQ_GLOBAL penalises end gaps; PF_SEQ_LOCAL is
+ * Smith-Waterman (the largest cell, of equal ones the smallest i, then j).  Traceback ties: diagonal, then F (x against a gap), then E;
+ * "opened" before "extended".  identity = n_ident / n_columns (NaN without columns); the span [x_lo,x_hi) x [y_lo,y_hi) and x2y [P,64]
+ * (optional; -1: a gap or outside the span) are in compacted coordinates.  Fill: score INT_MIN, counts and span -1, identity NaN.
+ *
+ * pf_seq_search_fwd: each query aa / mask [Q,N] against the library db_aa [D,Ld] (compact, Ld <= 64; an entry with db_len outside
+ * [0, Ld] is never the best): the entry of the highest alignment score, of equal scores the lowest index; the Q x D scores are never
+ * stored.  A query above PF_SEQ_MAX_LEN, or no valid entry: best_index -1, best_score INT_MIN, counts -1, identity NaN. */
+#define PF_SEQ_MAX_LEN 64
+#define PF_SEQ_TYPES 21
+#define PF_SEQ_MAX_GAP 4096
+#define PF_SEQ_GLOBAL 0
+#define PF_SEQ_LOCAL 1
+typedef struct {
+    const int64_t* aa_x; const int64_t* aa_y;                       /* [Bx,N], [By,N] */
+    const unsigned char* mx; const unsigned char* my;               /* [Bx,N], [By,N] */
+    const int* pairs;                                               /* [P,2] */
+    double* ratio;                                                  /* [P] */
+    int* matches; int* total; int* len_x; int* len_y;               /* [P] */
+    int* blocks; int* n_blocks;                                     /* [P,64,3], [P] optional */
+    int Bx, By, N, P;
+} pf_seq_ratio_args;
+int pf_seq_ratio_fwd(const pf_seq_ratio_args* a, pf_stream_t stream);
+
+typedef struct {
+    const int64_t* aa_x; const int64_t* aa_y;                       /* [Bx,N], [By,N] */
+    const unsigned char* mx; const unsigned char* my;               /* [Bx,N], [By,N] */
+    const int* pairs;                                               /* [P,2] */
+    const signed char* matrix;                                      /* [21,21] */
+    int* score; int* n_ident; int* n_aligned; int* n_columns;       /* [P] */
+    int* x_lo; int* x_hi; int* y_lo; int* y_hi;                     /* [P] */
+    int* len_x; int* len_y;                                         /* [P] */
+    double* identity;                                               /* [P] */
+    int* x2y;                                                       /* [P,64] optional */
+    int Bx, By, N, P;
+    int mode, gap_open, gap_extend;
+} pf_seq_align_args;
+int pf_seq_align_fwd(const pf_seq_align_args* a, pf_stream_t stream);
+
+typedef struct {
+    const int64_t* aa;                                              /* [Q,N] */
+    const unsigned char* mask;                                      /* [Q,N] */
+    const int64_t* db_aa;                                           /* [D,Ld] */
+    const int* db_len;                                              /* [D] */
+    const signed char* matrix;                                      /* [21,21] */
+    int* best_index; int* best_score; int* best_n_ident; int* best_n_columns;   /* [Q] */
+    double* best_identity;                                          /* [Q] */
+    int Q, N, D, Ld;
+    int mode, gap_open, gap_extend;
+} pf_seq_search_args;
+int pf_seq_search_fwd(const pf_seq_search_args* a, pf_stream_t stream);
+
 /* ---- lDDT and interface contacts (ABI 64, added entry points) ------------------------------------------------------------------
  * Both take the work-list family of pf_sidechain_compare_fwd: pair p = (i, j) of pairs [P,2] looks at the model x[i] and the reference
  * structure y[j] (y may alias x); group / query [By,N] belong to y; a pair with an index out of range gives zeros (min_dist: +inf).

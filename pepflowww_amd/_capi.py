@@ -273,6 +273,24 @@ class PolarArgs(C.Structure):
                 ("salt_max", C.c_float)]
 
 
+class SeqRatioArgs(C.Structure):
+    _fields_ = [("aa_x", _fp), ("aa_y", _fp), ("mx", _fp), ("my", _fp), ("pairs", _fp), ("ratio", _fp), ("matches", _fp), ("total", _fp),
+                ("len_x", _fp), ("len_y", _fp), ("blocks", _fp), ("n_blocks", _fp), ("Bx", _i), ("By", _i), ("N", _i), ("P", _i)]
+
+
+class SeqAlignArgs(C.Structure):
+    _fields_ = [("aa_x", _fp), ("aa_y", _fp), ("mx", _fp), ("my", _fp), ("pairs", _fp), ("matrix", _fp), ("score", _fp), ("n_ident", _fp),
+                ("n_aligned", _fp), ("n_columns", _fp), ("x_lo", _fp), ("x_hi", _fp), ("y_lo", _fp), ("y_hi", _fp), ("len_x", _fp),
+                ("len_y", _fp), ("identity", _fp), ("x2y", _fp), ("Bx", _i), ("By", _i), ("N", _i), ("P", _i), ("mode", _i),
+                ("gap_open", _i), ("gap_extend", _i)]
+
+
+class SeqSearchArgs(C.Structure):
+    _fields_ = [("aa", _fp), ("mask", _fp), ("db_aa", _fp), ("db_len", _fp), ("matrix", _fp), ("best_index", _fp), ("best_score", _fp),
+                ("best_n_ident", _fp), ("best_n_columns", _fp), ("best_identity", _fp), ("Q", _i), ("N", _i), ("D", _i), ("Ld", _i),
+                ("mode", _i), ("gap_open", _i), ("gap_extend", _i)]
+
+
 class LddtArgs(C.Structure):
     _fields_ = [("pos_x", _fp), ("pos_y", _fp), ("mask_x", _fp), ("mask_y", _fp), ("aa_x", _fp), ("aa_y", _fp), ("pairs", _fp),
                 ("group", _fp), ("query", _fp), ("scored", _fp), ("kept", _fp), ("scored_cross", _fp), ("kept_cross", _fp),
@@ -432,6 +450,9 @@ _SIGNATURES = {
     "pf_torsions_fwd": ([C.POINTER(TorsionsArgs), _fp], _i),
     "pf_sidechain_compare_fwd": ([C.POINTER(SidechainCompareArgs), _fp], _i),
     "pf_polar_fwd": ([C.POINTER(PolarArgs), _fp], _i),
+    "pf_seq_ratio_fwd": ([C.POINTER(SeqRatioArgs), _fp], _i),
+    "pf_seq_align_fwd": ([C.POINTER(SeqAlignArgs), _fp], _i),
+    "pf_seq_search_fwd": ([C.POINTER(SeqSearchArgs), _fp], _i),
     "pf_lddt_fwd": ([C.POINTER(LddtArgs), _fp], _i),
     "pf_contacts_fwd": ([C.POINTER(ContactsArgs), _fp], _i),
     "pf_cluster_fwd": ([C.POINTER(ClusterArgs), _fp], _i),

@@ -14,6 +14,9 @@ Input families, one binding path each:
                     and single / complete / average linkage clusters of the samples of each group, their representatives and the
                     best-scored member of each.  The linkages are checked against scipy's fcluster(criterion="distance"), as
                     partitions only; gromos follows the publication (Daura et al. 1999) and is not checked against GROMACS.
+  sequences         residue types aa [B,N] with masks and `pairs` [P,2] -- `_seq_pair_inputs`: sequence_ratio (pf_seq_ratio_fwd: difflib's
+                    SequenceMatcher ratio, the reference's diff_ratio), sequence_align (pf_seq_align_fwd: Gotoh, global / local, a caller's
+                    matrix) and their pairwise_sequence_* matrices; sequence_search (pf_seq_search_fwd) against a compact library.
 `_bind_in` / `_bind_out` fill the struct, `_as_bool` turns the byte outputs into bool, `_table` keeps the per-device constant tables.
 
 Deviation from the reference: `batch_align` selects each sample's masked atoms on their own.  The reference's
@@ -301,6 +304,197 @@ def pairwise_tm_align(x, mask, groups=None):
     pairs = _within_groups(B, groups)
     max_len = int(torch.as_tensor(mask).bool().sum(1).max()) if B else 0
     return _mirrored(B, pairs, x.device, (tm_align(x, x, mask, mask, pairs, max_len=max_len)["tm"], 1.0))[0]
+
+
+SEQ_MAX_LEN = 64            # PF_SEQ_MAX_LEN: the longest compacted sequence the pf_seq_* kernels take
+SEQ_TYPES = 21              # PF_SEQ_TYPES: the 20 residue types and X (every type outside 0..19)
+SEQ_MAX_GAP = 4096          # PF_SEQ_MAX_GAP
+SEQ_MODES = ("global", "local")     # PF_SEQ_GLOBAL, PF_SEQ_LOCAL
+SEQ_INT_MIN = -2 ** 31      # the fill value of a score
+
+
+def match_matrix(match=1, mismatch=-1):
+    """-> [21,21] int8 (CPU): `match` on the diagonal (X against X included), `mismatch` elsewhere.  The default scoring of
+    sequence_align; no published substitution table is shipped, callers pass their own [21,21] matrix."""
+    m = torch.full((SEQ_TYPES, SEQ_TYPES), int(mismatch), dtype=torch.int64)
+    m.fill_diagonal_(int(match))
+    return _check_matrix(m)
+
+
+def _check_matrix(matrix):
+    """-> the [21,21] integer matrix as int8 (where it is), entries in [-128, 127] (ValueError)"""
+    if not isinstance(matrix, torch.Tensor) or tuple(matrix.shape) != (SEQ_TYPES, SEQ_TYPES):
+        raise ValueError(f"matrix must be a [{SEQ_TYPES},{SEQ_TYPES}] tensor, got {tuple(getattr(matrix, 'shape', ()))}")
+    if matrix.is_floating_point() or matrix.is_complex() or matrix.dtype == torch.bool:
+        raise ValueError(f"matrix must hold integers, got {matrix.dtype}")
+    if matrix.dtype != torch.int8:
+        lo, hi = int(matrix.min()), int(matrix.max())
+        if lo < -128 or hi > 127:
+            raise ValueError(f"matrix entries must lie in [-128, 127], got [{lo}, {hi}]")
+    return matrix.to(torch.int8)
+
+
+def _seq_scoring(mode, matrix, gap_open, gap_extend):
+    """checks the scoring arguments of sequence_align / sequence_search (ValueError, before any device work)
+    -> bind(a, dev): sets them in the argument struct and returns the device matrix to keep alive"""
+    if mode not in SEQ_MODES:
+        raise ValueError(f"mode must be one of {SEQ_MODES}, got {mode!r}")
+    if int(gap_open) != gap_open or int(gap_extend) != gap_extend or not 0 <= gap_extend <= gap_open <= SEQ_MAX_GAP:
+        raise ValueError(f"gap penalties must be integers with 0 <= gap_extend <= gap_open <= {SEQ_MAX_GAP}, got {gap_open}, {gap_extend}")
+    checked = None if matrix is None else _check_matrix(matrix)
+
+    def bind(a, dev):
+        m = (_table("seq_match_matrix", dev, match_matrix) if checked is None else checked.to(dev)).contiguous()
+        _bind_in(a, matrix=m)
+        a.mode, a.gap_open, a.gap_extend = SEQ_MODES.index(mode), int(gap_open), int(gap_extend)
+        return m
+    return bind
+
+
+def _seq_pair_inputs(a, name, aa_x, aa_y, mx, my, pairs):
+    """The pair-work-list family on residue types: checks aa_x, mx [Bx,N], aa_y, my [By,N], pairs [P,2] (ValueError), converts (aa_y is
+    aa_x and my is mx share one buffer) and binds them with Bx, By, N, P into `a`.  -> (the tensors to keep alive, device, P)"""
+    for nm, t in (("aa_x", aa_x), ("aa_y", aa_y), ("mx", mx), ("my", my)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{name}: {nm} must be a [B,N] tensor, got {tuple(getattr(t, 'shape', ()))}")
+    for nm, t in (("aa_x", aa_x), ("aa_y", aa_y)):
+        if t.is_floating_point() or t.dtype == torch.bool:
+            raise ValueError(f"{name}: {nm} must hold integer residue types, got {t.dtype}")
+    Bx, N = aa_x.shape
+    By = aa_y.shape[0]
+    if aa_y.shape[1] != N or tuple(mx.shape) != (Bx, N) or tuple(my.shape) != (By, N):
+        raise ValueError(f"shapes do not agree: aa_x {tuple(aa_x.shape)}, aa_y {tuple(aa_y.shape)}, mx {tuple(mx.shape)}, my {tuple(my.shape)}")
+    pairs = _check_pairs(pairs)
+    if N == 0 or Bx == 0 or By == 0:
+        raise ValueError(f"{name} needs at least one sequence slot of at least one residue on each side")
+    dev = aa_x.device
+    kx, kmx = aa_x.to(dev, torch.int64).contiguous(), _bytes(mx, dev)
+    keep = [kx, kx if aa_y is aa_x else aa_y.to(dev, torch.int64).contiguous(), kmx, kmx if my is mx else _bytes(my, dev),
+            pairs.to(dev, torch.int32).contiguous()]
+    _bind_in(a, aa_x=keep[0], aa_y=keep[1], mx=keep[2], my=keep[3], pairs=keep[4])
+    a.Bx, a.By, a.N, a.P = Bx, By, N, pairs.shape[0]
+    return keep, dev, pairs.shape[0]
+
+
+def sequence_ratio(aa_x, aa_y, mx, my, pairs, blocks=False):
+    """pf_seq_ratio_fwd: difflib.SequenceMatcher(None, a, b).ratio() -- the reference's `diff_ratio` (eval/geometry.py) -- for every
+    pair (i, j) of `pairs` [P,2], with a = the types aa_x[i] where mx[i] is set, in order, and b = aa_y[j] where my[j] is set.  The
+    conventions (difflib's tie-breaking, no junk) are listed in csrc/seqalign.hip.
+
+    aa_x [Bx,N], aa_y [By,N] integer residue types (a type outside 0..19 is X, and X equals X), mx [Bx,N], my [By,N]; N is not
+    bounded, the sequences (the set residues) may have up to SEQ_MAX_LEN = 64 residues and may be empty.
+    -> dict of device tensors: ratio [P] float64 = 2.0 * matches / total (1.0 when both are empty), bit-equal to difflib's;
+    matches, total, len_x, len_y [P] int32; with `blocks`: blocks [P,64,3] int32, the (i, j, k) of get_matching_blocks() without its
+    sentinel, unused rows (-1, -1, 0), and n_blocks [P].
+    A sequence above 64 residues or a pair index out of range: ratio NaN, matches, total and n_blocks -1.  The ratio is not symmetric
+    in (a, b)."""
+    a = _capi.SeqRatioArgs()
+    keep, dev, P = _seq_pair_inputs(a, "sequence_ratio", aa_x, aa_y, mx, my, pairs)
+    out = {"ratio": torch.empty(P, dtype=torch.float64, device=dev)}
+    for k in ("matches", "total", "len_x", "len_y"):
+        out[k] = torch.empty(P, dtype=torch.int32, device=dev)
+    if blocks:
+        out["blocks"] = torch.empty(P, SEQ_MAX_LEN, 3, dtype=torch.int32, device=dev)
+        out["n_blocks"] = torch.empty(P, dtype=torch.int32, device=dev)
+    _bind_out(a, out)
+    if P:
+        _capi.check(_capi.load().pf_seq_ratio_fwd(C.byref(a), _capi.stream_ptr()), "pf_seq_ratio_fwd")
+    return out
+
+
+def sequence_align(aa_x, aa_y, mx, my, pairs, mode="global", matrix=None, gap_open=2, gap_extend=1, alignment=False):
+    """pf_seq_align_fwd: Gotoh's affine-gap pairwise alignment of the sequences of every pair of `pairs` [P,2] (inputs as in
+    `sequence_ratio`), in int32 on the device.  The recurrences and the traceback's tie rules are listed in csrc/seqalign.hip.
+
+    mode: "global" (Needleman-Wunsch with penalised end gaps) or "local" (Smith-Waterman; of equal best cells the smallest x index,
+    then the smallest y index).  matrix: [21,21] integers in [-128, 127], matrix[x type][y type] (None: match_matrix(), +1 / -1);
+    no substitution table is shipped.  A gap of length g costs gap_open + (g - 1) gap_extend, 0 <= gap_extend <= gap_open <= 4096.
+    -> dict of device tensors [P]: score, n_ident (columns of equal types), n_aligned (columns without a gap), n_columns, x_lo,
+    x_hi, y_lo, y_hi (the aligned span [lo, hi) in the compacted sequences; the whole sequences in global mode), len_x, len_y int32;
+    identity float64 = n_ident / n_columns (needle's / water's definition; NaN without columns -- the counts are there for another
+    denominator); with `alignment`: x2y [P,64] int32, the y index aligned to the k-th residue of x (-1: a gap or outside the span).
+    A sequence above 64 residues or a pair index out of range: score SEQ_INT_MIN, the counts and the span -1, identity NaN."""
+    a = _capi.SeqAlignArgs()
+    scoring = _seq_scoring(mode, matrix, gap_open, gap_extend)
+    keep, dev, P = _seq_pair_inputs(a, "sequence_align", aa_x, aa_y, mx, my, pairs)
+    keep.append(scoring(a, dev))
+    out = {k: torch.empty(P, dtype=torch.int32, device=dev)
+           for k in ("score", "n_ident", "n_aligned", "n_columns", "x_lo", "x_hi", "y_lo", "y_hi", "len_x", "len_y")}
+    out["identity"] = torch.empty(P, dtype=torch.float64, device=dev)
+    if alignment:
+        out["x2y"] = torch.empty(P, SEQ_MAX_LEN, dtype=torch.int32, device=dev)
+    _bind_out(a, out)
+    if P:
+        _capi.check(_capi.load().pf_seq_align_fwd(C.byref(a), _capi.stream_ptr()), "pf_seq_align_fwd")
+    return out
+
+
+def sequence_search(aa, mask, db_aa, db_len, mode="global", matrix=None, gap_open=2, gap_extend=1):
+    """pf_seq_search_fwd: for each query (the types aa[q] where mask[q] is set; aa, mask [Q,N]) the entry of the library with the
+    highest `sequence_align` score, of equal scores the lowest index -- "the closest known peptide".  db_aa [D,Ld] integer types,
+    already compact (entry d is db_aa[d, :db_len[d]]), Ld <= 64; db_len [D]; an entry whose length is outside [0, Ld] is never the
+    best.  mode / matrix / gap_open / gap_extend as in `sequence_align`.  The Q x D scores are never stored: one workgroup per query.
+    -> dict of device tensors [Q]: best_index, best_score, best_n_ident, best_n_columns int32, best_identity float64.
+    A query above 64 residues, or an empty library: best_index -1, best_score SEQ_INT_MIN, the counts -1, best_identity NaN."""
+    for nm, t in (("aa", aa), ("mask", mask), ("db_aa", db_aa)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"sequence_search: {nm} must be a 2-d tensor, got {tuple(getattr(t, 'shape', ()))}")
+    for nm, t in (("aa", aa), ("db_aa", db_aa)):
+        if t.is_floating_point() or t.dtype == torch.bool:
+            raise ValueError(f"sequence_search: {nm} must hold integer residue types, got {t.dtype}")
+    Q, N = aa.shape
+    D, Ld = db_aa.shape
+    db_len = torch.as_tensor(db_len)
+    if tuple(mask.shape) != (Q, N) or tuple(db_len.shape) != (D,):
+        raise ValueError(f"shapes do not agree: aa {tuple(aa.shape)}, mask {tuple(mask.shape)}, db_aa {tuple(db_aa.shape)}, "
+                         f"db_len {tuple(db_len.shape)}")
+    if N == 0:
+        raise ValueError("sequence_search needs query slots of at least one residue")
+    if not 1 <= Ld <= SEQ_MAX_LEN:
+        raise ValueError(f"library entries have 1 to {SEQ_MAX_LEN} slots, got Ld = {Ld}")
+    scoring = _seq_scoring(mode, matrix, gap_open, gap_extend)
+    a = _capi.SeqSearchArgs()
+    dev = aa.device
+    keep = [aa.to(dev, torch.int64).contiguous(), _bytes(mask, dev), db_aa.to(dev, torch.int64).contiguous(),
+            db_len.to(dev, torch.int32).contiguous()]
+    keep.append(scoring(a, dev))
+    _bind_in(a, aa=keep[0], mask=keep[1])
+    if D:
+        _bind_in(a, db_aa=keep[2], db_len=keep[3])
+    a.Q, a.N, a.D, a.Ld = Q, N, D, Ld
+    out = {k: torch.empty(Q, dtype=torch.int32, device=dev) for k in ("best_index", "best_score", "best_n_ident", "best_n_columns")}
+    out["best_identity"] = torch.empty(Q, dtype=torch.float64, device=dev)
+    _bind_out(a, out)
+    if Q:
+        _capi.check(_capi.load().pf_seq_search_fwd(C.byref(a), _capi.stream_ptr()), "pf_seq_search_fwd")
+    return out
+
+
+def _mirrored_f64(B, pairs, dev, values, diag):
+    """`_mirrored` for one float64 [P] result (the sequence ratios and identities are float64 quotients of integers)"""
+    i, j = pairs[:, 0].to(dev, torch.int64), pairs[:, 1].to(dev, torch.int64)
+    m = torch.full((B, B), float("nan"), dtype=torch.float64, device=dev)
+    m[i, j] = values
+    m[j, i] = values
+    return m.masked_fill(torch.eye(B, dtype=torch.bool, device=dev), diag)
+
+
+def pairwise_sequence_ratio(aa, mask, groups=None):
+    """aa, mask [B,N] -> ratio [B,B] float64: `sequence_ratio` of every pair i < j of the same group (all one group when `groups` is
+    None), mirrored, with a diagonal of 1; pairs across groups are NaN.  difflib's ratio depends on the direction (about a quarter
+    of random short pairs over four letters differ): the one kept is a = sequence i, b = sequence j with i < j."""
+    B = aa.shape[0]
+    pairs = _within_groups(B, groups)
+    return _mirrored_f64(B, pairs, aa.device, sequence_ratio(aa, aa, mask, mask, pairs)["ratio"], 1.0)
+
+
+def pairwise_sequence_identity(aa, mask, groups=None, **align):
+    """aa, mask [B,N] -> identity [B,B] float64: the `sequence_align` identity (n_ident / n_columns; **align: mode, matrix, gap_open,
+    gap_extend) of every pair i < j of the same group, x = sequence i, y = sequence j, mirrored, with a diagonal of 1; pairs across
+    groups are NaN (and so is a pair without an aligned column).  1 - this matrix is a `dist` that `cluster` takes."""
+    B = aa.shape[0]
+    pairs = _within_groups(B, groups)
+    return _mirrored_f64(B, pairs, aa.device, sequence_align(aa, aa, mask, mask, pairs, **align)["identity"], 1.0)
 
 
 CLUSTER_MAX_N = 1024        # PF_CLUSTER_MAX_N: the most samples one group may hold

@@ -18,10 +18,11 @@ scipy's fcluster(criterion="distance") as partitions only); rotamer side chains 
 scored with the interface energy's pair function and chosen by iterated conditional modes, which is not SCWRL4 and not Rosetta's
 packer and takes their place in role only (`pack_samples`, and backbone="packed" in the structure metrics); point-mutation scanning of
 the generated residues, an alanine scan and a position scan with the packer's self energy on an unmoved environment, which is not FoldX
-(eval/foldx.py) and not Rosetta and takes their place in role only (`mutation_scan`).
+(eval/foldx.py) and not Rosetta and takes their place in role only (`mutation_scan`); the reference's `diff_ratio` (difflib's SequenceMatcher ratio, exact values), an
+alignment identity across lengths and the nearest known sequence of a library (`sequence_scores`).
 
 Every per-residue, per-point and per-atom-pair operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd /
-pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_polar_fwd / pf_relax_fwd / pf_cluster_fwd / pf_pack_sidechains_fwd / pf_mutation_scan_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
+pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_polar_fwd / pf_relax_fwd / pf_cluster_fwd / pf_pack_sidechains_fwd / pf_mutation_scan_fwd / pf_seq_ratio_fwd / pf_seq_align_fwd / pf_seq_search_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
@@ -218,6 +219,53 @@ def structure_scores(final, batch, groups=None, novelty_tm=0.5, novelty_ident=0.
     div_tm = 1.0 - _group_sum(ptm, gidx, G) / _group_sum(torch.ones_like(gidx), gidx, G)
     return {"tm": tm, "tm_pooled": tm.double().mean(), "novel": novel, "novelty": novelty, "diversity_tm": div_tm,
             "group_labels": glab}
+
+
+def sequence_scores(final, batch, groups=None, known=None, novelty_ident=0.5, **align):
+    """The sequence side of the evaluation for peptides of any length: the reference's `diff_ratio` (eval/geometry.py: the
+    difflib.SequenceMatcher ratio), an alignment identity and, against a library of known sequences, the nearest known peptide.
+    final / batch / groups as in `evaluate_samples` (final["trans"], ["trans_1"], ["seqs"], ["seqs_1"] and batch["generate_mask"] are
+    read).  A sample's sequence is its generated residues, in order, at most geometry.SEQ_MAX_LEN = 64 of them (above: NaN).
+    **align: mode, matrix, gap_open, gap_extend of geometry.sequence_align (global, +1 / -1, 2, 1).
+
+    -> dict of device tensors:
+      seq_ratio       [B] float64: SequenceMatcher(None, sample, native).ratio(), the argument order of diff_ratio(sample, native),
+                      bit-equal to difflib's;
+      aar             [B] positional identity, as `evaluate_samples` gives it;
+      align_identity  [B] float64: identical columns over all columns of the alignment of the sample with the native;
+      diversity_seq   [G] float64: 1 - the mean ratio over the pairs i < j of the group (a = sample i, b = sample j), NaN for a group
+                      of one;
+      group_labels    [G];
+    with known = (db_aa [D,Ld], db_len [D]), a library of compact sequences (geometry.sequence_search):
+      nearest_known   [B] int32: the entry with the highest alignment score against the sample (lowest index of equal scores; -1 for
+                      an empty library);
+      nearest_identity [B] float64: the identity of that alignment;
+      novel_seq       [B] bool: nearest_identity < novelty_ident (False where there is no nearest entry).
+    `diversity_seq`, `novel_seq` and the thresholds are this package's definitions."""
+    labels = _check_groups(batch["generate_mask"], groups)
+    dev = _device(batch["generate_mask"], final["trans"])
+    final = {k: final[k].to(dev) for k in ("trans", "seqs", "trans_1", "seqs_1")}
+    B = final["seqs"].shape[0]
+    gen = batch["generate_mask"].to(dev).bool()
+    ids = torch.arange(B, dtype=torch.int32)
+    diag = torch.stack([ids, ids], 1)
+
+    ratio = geometry.sequence_ratio(final["seqs"], final["seqs_1"], gen, gen, diag)["ratio"]
+    ident = geometry.sequence_align(final["seqs"], final["seqs_1"], gen, gen, diag, **align)["identity"]
+    aar = superpose(final["trans"], final["trans_1"], gen, gen, diag, aa_x=final["seqs"], aa_y=final["seqs_1"])["ident"]
+
+    pairs, gidx, glab = group_pairs(labels)
+    gidx = gidx.to(dev)
+    G = glab.numel()
+    pr = geometry.sequence_ratio(final["seqs"], final["seqs"], gen, gen, pairs)["ratio"]
+    div_seq = 1.0 - _group_sum(pr, gidx, G) / _group_sum(torch.ones_like(gidx), gidx, G)
+    out = {"seq_ratio": ratio, "aar": aar, "align_identity": ident, "diversity_seq": div_seq, "group_labels": glab.to(dev)}
+    if known is not None:
+        db_aa, db_len = known
+        near = geometry.sequence_search(final["seqs"], gen, db_aa.to(dev), torch.as_tensor(db_len).to(dev), **align)
+        out["nearest_known"], out["nearest_identity"] = near["best_index"], near["best_identity"]
+        out["novel_seq"] = near["best_identity"] < novelty_ident
+    return out
 
 
 CLUSTER_METRICS = ("rmsd", "pose_rmsd", "tm", "tmalign")
