@@ -1699,6 +1699,72 @@ typedef struct {
 int pf_mutation_scan_fwd(const pf_mutation_scan_args* a, pf_stream_t stream);
 int pf_mutation_scan_work_bytes(int B, int N);
 
+/* ---- fixed-backbone sequence design (ABI 65, added entry points) --------------------------------------------------------------------
+ * pf_sequence_design_fwd: residue TYPE and rotamer of the designed residues of each structure are chosen together, on the fixed
+ * backbone, by iterated conditional modes over every candidate (type, rotamer): pf_mutation_scan_fwd's E_self of every candidate
+ * against the residues that are not designed, plus the pair terms between the designed residues, whose CB, radii and type bits follow
+ * their current type; the conventions are listed in csrc/seqdesign.hip.  It stands where the reference's eval/run_mpnn.py runs
+ * ProteinMPNN over backbone-only samples, in role only: it is NOT ProteinMPNN and NOT Rosetta fixbb.  The energy is this package's
+ * Vina-form pair energy plus the rotamer table's energy plus the caller's per-type reference energy: no solvation, no electrostatics,
+ * no entropy, no learned prior; without reference energies it favours large side chains; a deterministic local search; untuned.
+ * Tables, rotamer table, cutoff, weights, pro, cys and sweeps as pf_pack_args.  A residue is designed where `designed` is set, its type
+ * is in 0..19 and its N, CA and C are present; its candidates are the types whose byte is set (null: all 20; none set: its own type).
+ * A sample with more than max_res (<= PF_SEQ_DESIGN_MAX_RES) such residues gets status 1 and comes back as if none were designed.
+ *   aa_out [B,N]; pos_out [B,N,15,3], mask_out [B,N,15] as pf_pack_sidechains_fwd; designed_out [B,N]; status [B]; rotamer [B,N] (-1);
+ *   chi [B,N,4]; n_candidates [B,N] (0); energy_self_best [B,N] (E_self of the start); energy_residue [B,N] (E_self + half the pair
+ *   terms at the end); energy_trace [B,sweeps+1] float64; sweeps_run [B]; changed, changed_types [B,sweeps]; profile [B,N,20] (the
+ *   smallest conditional energy of each candidate type against the final state of the others; +inf), profile_rotamer [B,N,20] (-1);
+ *   choice_trace [B,sweeps,N,2] optional: type and rotamer taken at each visit (entries not visited are left as they are).
+ * work: pf_sequence_design_work_bytes(B, N, max_rot, max_res) bytes = B (16 + 276 N + max_res (4 + 80 + 80 max_rot)), 16-byte aligned,
+ * no initialisation needed (-1: N > PF_PACK_MAX_N, max_rot or max_res out of range, a negative size, or more than INT_MAX bytes).
+ * Three launches, no atomics, one writer per output, every sum in a fixed order, every decision an argmin under (value, type,
+ * rotamer): bit-identical from run to run and independent of the rest of the batch; the host reads nothing back. */
+#define PF_SEQ_DESIGN_MAX_RES 64
+#define PF_SEQ_DESIGN_TYPES 20
+typedef struct {
+    const float* pos;                                               /* [B,N,n_atoms,3] */
+    const unsigned char* atom_mask;                                 /* [B,N,n_atoms] */
+    const int64_t* aa;                                              /* [B,N] */
+    const int* residue_index;                                       /* [B,N] */
+    const unsigned char* designed;                                  /* [B,N] */
+    const unsigned char* candidates;                                /* [B,N,20] optional */
+    const float* ref_energy;                                        /* [20] optional */
+    const float* radius;                                            /* [21,15] as pf_pack_args, down to rot_energy */
+    const unsigned char* types;                                     /* [21,15] */
+    const int* own_mask;                                            /* [21,15] */
+    const float* tab_rot;                                           /* [21,8,9] */
+    const float* tab_trans;                                         /* [21,8,3] */
+    const int* tab_group;                                           /* [21,14] */
+    const float* tab_pos;                                           /* [21,14,3] */
+    const unsigned char* tab_mask;                                  /* [22,15] */
+    const float* rot_chi;                                           /* [21,max_rot,4] radians */
+    const int* rot_count;                                           /* [21] */
+    const float* rot_energy;                                        /* [21,max_rot] */
+    void* work;                                                     /* pf_sequence_design_work_bytes(B, N, max_rot, max_res) bytes */
+    int64_t* aa_out;                                                /* [B,N] */
+    float* pos_out;                                                 /* [B,N,15,3] */
+    unsigned char* mask_out;                                        /* [B,N,15] */
+    unsigned char* designed_out;                                    /* [B,N] */
+    int* status;                                                    /* [B] */
+    int* rotamer;                                                   /* [B,N] */
+    float* chi;                                                     /* [B,N,4] */
+    int* n_candidates;                                              /* [B,N] */
+    float* energy_self_best;                                        /* [B,N] */
+    float* energy_residue;                                          /* [B,N] */
+    double* energy_trace;                                           /* [B,sweeps+1] */
+    int* sweeps_run;                                                /* [B] */
+    int* changed;                                                   /* [B,sweeps]; may be null when sweeps is 0 */
+    int* changed_types;                                             /* [B,sweeps]; may be null when sweeps is 0 */
+    float* profile;                                                 /* [B,N,20] */
+    int* profile_rotamer;                                           /* [B,N,20] */
+    int* choice_trace;                                              /* [B,sweeps,N,2] optional */
+    int B, N, n_atoms, max_rot, max_res, sweeps, pro, cys;
+    float cutoff;                                                   /* > 0; 8.0 */
+    float w_gauss1, w_gauss2, w_repulsion, w_hydrophobic, w_hbond;  /* -0.0356, -0.00516, 0.840, -0.0351, -0.587 */
+} pf_sequence_design_args;
+int pf_sequence_design_fwd(const pf_sequence_design_args* a, pf_stream_t stream);
+int pf_sequence_design_work_bytes(int B, int N, int max_rot, int max_res);
+
 /* ---- empirical interface energy (ABI 64, added entry point) -----------------------------------------------------------------------
  * pf_interface_energy_fwd: the functional form of AutoDock Vina's scoring function (Trott & Olson, J. Comput. Chem. 2010) over the
  * heavy atoms of a batch of structures, between atoms of residues whose group bytes differ; the conventions are listed in

@@ -333,6 +333,19 @@ class MutationScanArgs(C.Structure):
                 ("w_hydrophobic", C.c_float), ("w_hbond", C.c_float)]
 
 
+class SeqDesignArgs(C.Structure):
+    _fields_ = [("pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("residue_index", _fp), ("designed", _fp), ("candidates", _fp),
+                ("ref_energy", _fp), ("radius", _fp), ("types", _fp), ("own_mask", _fp), ("tab_rot", _fp), ("tab_trans", _fp),
+                ("tab_group", _fp), ("tab_pos", _fp), ("tab_mask", _fp), ("rot_chi", _fp), ("rot_count", _fp), ("rot_energy", _fp),
+                ("work", _fp), ("aa_out", _fp), ("pos_out", _fp), ("mask_out", _fp), ("designed_out", _fp), ("status", _fp),
+                ("rotamer", _fp), ("chi", _fp), ("n_candidates", _fp), ("energy_self_best", _fp), ("energy_residue", _fp),
+                ("energy_trace", _fp), ("sweeps_run", _fp), ("changed", _fp), ("changed_types", _fp), ("profile", _fp),
+                ("profile_rotamer", _fp), ("choice_trace", _fp),
+                ("B", _i), ("N", _i), ("n_atoms", _i), ("max_rot", _i), ("max_res", _i), ("sweeps", _i), ("pro", _i), ("cys", _i),
+                ("cutoff", C.c_float), ("w_gauss1", C.c_float), ("w_gauss2", C.c_float), ("w_repulsion", C.c_float),
+                ("w_hydrophobic", C.c_float), ("w_hbond", C.c_float)]
+
+
 class InterfaceEnergyArgs(C.Structure):
     _fields_ = [("pos", _fp), ("atom_mask", _fp), ("aa", _fp), ("group", _fp), ("query", _fp), ("radius", _fp), ("types", _fp),
                 ("work", _fp), ("terms_atom", _fp), ("terms_residue", _fp), ("energy_residue", _fp), ("pairs_atom", _fp),
@@ -461,6 +474,8 @@ _SIGNATURES = {
     "pf_pack_work_bytes": ([_i, _i, _i], _i),
     "pf_mutation_scan_fwd": ([C.POINTER(MutationScanArgs), _fp], _i),
     "pf_mutation_scan_work_bytes": ([_i, _i], _i),
+    "pf_sequence_design_fwd": ([C.POINTER(SeqDesignArgs), _fp], _i),
+    "pf_sequence_design_work_bytes": ([_i, _i, _i, _i], _i),
     "pf_interface_energy_fwd": ([C.POINTER(InterfaceEnergyArgs), _fp], _i),
     "pf_relax_energy_fwd": ([C.POINTER(RelaxArgs), _fp], _i),
     "pf_relax_fwd": ([C.POINTER(RelaxArgs), _fp], _i),

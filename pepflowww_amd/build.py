@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpepflow_hip.so")
-SOURCES = ["selftest.hip", "linear.hip", "edge_transition.hip", "edge_transition_v3.hip", "edge_transition_v4.hip", "edge_transition_v5.hip", "ipa_attn.hip", "ipa_split.hip", "node_ops.hip", "flow_step.hip", "guidance.hip", "temper.hip", "steer.hip", "encode.hip", "node_track.hip", "train_fwd.hip", "backward.hip", "ipa_bwd.hip", "et_bwd.hip", "optimizer.hip", "full_atom.hip", "superpose.hip", "tm_score.hip", "dssp.hip", "tm_align.hip", "violations.hip", "sasa.hip", "cavity.hip", "torsions.hip", "polar.hip", "seqalign.hip", "mutscan.hip", "lddt.hip", "contacts.hip", "clustering.hip", "packing.hip", "interface_energy.hip", "relax.hip"]
+SOURCES = ["selftest.hip", "linear.hip", "edge_transition.hip", "edge_transition_v3.hip", "edge_transition_v4.hip", "edge_transition_v5.hip", "ipa_attn.hip", "ipa_split.hip", "node_ops.hip", "flow_step.hip", "guidance.hip", "temper.hip", "steer.hip", "encode.hip", "node_track.hip", "train_fwd.hip", "backward.hip", "ipa_bwd.hip", "et_bwd.hip", "optimizer.hip", "full_atom.hip", "superpose.hip", "tm_score.hip", "dssp.hip", "tm_align.hip", "violations.hip", "sasa.hip", "cavity.hip", "torsions.hip", "polar.hip", "seqalign.hip", "mutscan.hip", "seqdesign.hip", "lddt.hip", "contacts.hip", "clustering.hip", "packing.hip", "interface_energy.hip", "relax.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize, every file: hipcc's SLP vectoriser pairs independent scalar fp32 operations into packed ones (v_pk_mul_f32 /
 # v_pk_add_f32, with op_sel where the halves cross).  Round 5 traced EVERY run-to-run failure of the projecting score kernels to one such

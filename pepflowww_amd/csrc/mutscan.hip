@@ -152,6 +152,7 @@ struct ScanLds {
     int best_i[2];
 };
 
+// seqdesign.hip's self_kernel is this kernel's twin (the same rows, tiles, sums and order) and promises its bits: a change here belongs there.
 __global__ __launch_bounds__(NT) void scan_kernel(pf_mutation_scan_args a, Work w) {
     __shared__ ScanLds L;
     const int N = a.N, R = a.max_rot, A = a.n_atoms, tid = threadIdx.x, t = blockIdx.x, q = blockIdx.y;

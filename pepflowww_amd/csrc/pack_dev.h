@@ -1,5 +1,5 @@
-// Device helpers shared by packing.hip and mutscan.hip: the pair function, the backbone frame with the chi1 offset, the rotamer frame
-// chain and a residue's environment atoms.  Pure functions of their arguments; `Args` is pf_pack_args or pf_mutation_scan_args, which
+// Device helpers shared by packing.hip, mutscan.hip and seqdesign.hip: the pair function, the backbone frame with the chi1 offset, the rotamer frame
+// chain and a residue's environment atoms.  Pure functions of their arguments; `Args` is pf_pack_args, pf_mutation_scan_args or pf_sequence_design_args, which
 // name the tables, the rotamer table and the weights alike.  The conventions and the summation order are stated in packing.hip; the
 // operation order here is the one its oracle (tests/pack_oracle.py) restates, so nothing in this file may be reassociated.
 #pragma once

@@ -1877,6 +1877,116 @@ def mutation_scan(pos, atom_mask, aa, residue_index, positions, candidates=None,
     return out
 
 
+# Fixed-backbone sequence design (conventions: csrc/seqdesign.hip).  It is NOT ProteinMPNN (which the reference's eval/run_mpnn.py runs
+# over backbone-only samples) and NOT Rosetta fixbb: an iterated-conditional-modes search over type and rotamer with `pack_sidechains`'
+# own energy, no learned prior; it stands for them in role only.
+SEQ_DESIGN_MAX_RES = 64     # PF_SEQ_DESIGN_MAX_RES: designed residues per sample
+SEQ_DESIGN_TYPES = 20       # PF_SEQ_DESIGN_TYPES: the candidate residue types 0..19
+
+
+def _ref_energy(ref_energy):
+    """None or 20 finite numbers -> None or a [20] float32 CPU tensor (ValueError)"""
+    if ref_energy is None:
+        return None
+    try:
+        r = torch.as_tensor(ref_energy).detach().cpu().to(torch.float32)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"ref_energy must be None or {SEQ_DESIGN_TYPES} finite numbers, got {ref_energy!r}") from None
+    if tuple(r.shape) != (SEQ_DESIGN_TYPES,):
+        raise ValueError(f"ref_energy must be None or {SEQ_DESIGN_TYPES} finite numbers, got shape {tuple(r.shape)}")
+    if not bool(torch.isfinite(r).all()):
+        raise ValueError(f"ref_energy must be finite, got {r.tolist()}")
+    return r.contiguous()
+
+
+def design_sequence(pos, atom_mask, aa, residue_index, designed, candidates=None, ref_energy=None, rotamers=None, sweeps=8, cutoff=8.0,
+                    weights=VINA_WEIGHTS, trace=False):
+    """pf_sequence_design_fwd: fixed-backbone sequence design of the residues `designed` on the device (conventions: csrc/
+    seqdesign.hip).  The residue type AND the rotamer of every designed residue are chosen together by iterated conditional modes:
+    every rotamer of every candidate type is built on the residue's own backbone as `pack_sidechains` builds it; its energy is
+    `mutation_scan`'s E_self against the residues that are not designed (plus ref_energy[type]), plus the pair terms with the other
+    designed residues in their current types and rotamers -- CB, radii and type bits follow the current type -- and a sweep gives
+    every designed residue, in ascending position, the (type, rotamer) of smallest conditional energy.  Every accepted move lowers
+    the total energy; the search stops after a sweep that changed nothing, or after `sweeps`.
+
+    What it is, and is not: it stands where the reference's evaluation runs ProteinMPNN over backbone-only samples (eval/
+    run_mpnn.py), in role only.  It is NOT ProteinMPNN and NOT Rosetta fixbb: the energy is this package's Vina-form pair energy plus
+    the rotamer table's energy plus `ref_energy`; there is no solvation, no electrostatics, no entropy and no learned prior, and the
+    backbone does not move.  Without reference energies the energy favours large side chains (more atoms, more attractive pairs);
+    ref_energy is the caller's and none is shipped.  A deterministic local search, not the global minimum; the defaults are untuned.
+
+    Arguments as `pack_sidechains` with designed [B,N] in place of movable: a residue is designed where `designed` is set, its type
+    is in 0..19 and its N, CA and C are in atom_mask; every other residue is fixed environment and comes back bit for bit.
+    candidates: None (all 20 types), a [20] mask or a [B,N,20] mask; a residue whose set is empty keeps its type and is repacked.
+    ref_energy: None or 20 finite numbers added to the energy of every rotamer of the type.  At most SEQ_DESIGN_MAX_RES = 64
+    residues are designed in a sample: a sample with more gets status 1 and comes back as if nothing were designed (decided on the
+    device).  rotamers, sweeps, cutoff, weights as `pack_sidechains`.
+    -> dict of device tensors: aa [B,N] int64 (the designed types; others as given); pos [B,N,15,3] float32 and atom_mask [B,N,15]
+    bool as `pack_sidechains`; designed [B,N] bool; status [B] int32; rotamer [B,N] int32 (-1); chi [B,N,4] float32; n_candidates
+    [B,N] int32; energy_self_best [B,N] float32 (E_self of the start); energy_residue [B,N] float32 (E_self plus half the pair terms
+    at the end); energy_trace [B,sweeps+1] float64 ([0]: the start; sweeps not run repeat the last); sweeps_run [B] int32; changed,
+    changed_types [B,sweeps] int32 (residues whose (type, rotamer), whose type changed in each sweep); profile [B,N,20] float32 (the
+    smallest conditional energy of each candidate type against the final state of the others; +inf for a non-candidate) and
+    profile_rotamer [B,N,20] int32 (-1); with trace=True also choice_trace [B,sweeps,N,2] int32 (type and rotamer taken at each
+    visit, -1 where none)."""
+    if designed is None or residue_index is None:
+        raise ValueError("design_sequence needs residue_index [B,N] and designed [B,N]")
+    if not isinstance(sweeps, int) or isinstance(sweeps, bool) or sweeps < 0:
+        raise ValueError(f"sweeps must be an integer >= 0, got {sweeps!r}")
+    cutoff, w = _positive("cutoff", cutoff), _weights(weights)
+    rot = None if rotamers is None else _check_rotamers(rotamers)
+    ref = _ref_energy(ref_energy)
+    dev, (B, N, A), pos, atom_mask, (aa, residue_index, designed) = _structure(pos, atom_mask, (
+        ("aa", aa, torch.int64), ("residue_index", residue_index, torch.int32), ("designed", designed, torch.uint8)), max_n=PACK_MAX_N)
+    cand = _scan_candidates(candidates, B, N)
+    cand = None if cand is None else _bytes(cand, dev)
+    S, T = PACK_SLOTS, SEQ_DESIGN_TYPES
+    f32 = lambda *shape: torch.zeros(*shape, device=dev)  # noqa: E731
+    i32 = lambda *shape, fill=0: torch.full(shape, fill, dtype=torch.int32, device=dev)  # noqa: E731
+    out = {"aa": torch.zeros(B, N, dtype=torch.int64, device=dev), "pos": f32(B, N, S, 3),
+           "atom_mask": torch.zeros(B, N, S, dtype=torch.uint8, device=dev), "designed": torch.zeros(B, N, dtype=torch.uint8, device=dev),
+           "status": i32(B), "rotamer": i32(B, N, fill=-1), "chi": f32(B, N, 4), "n_candidates": i32(B, N),
+           "energy_self_best": f32(B, N), "energy_residue": f32(B, N),
+           "energy_trace": torch.zeros(B, sweeps + 1, dtype=torch.float64, device=dev), "sweeps_run": i32(B), "changed": i32(B, sweeps),
+           "changed_types": i32(B, sweeps), "profile": torch.full((B, N, T), float("inf"), device=dev),
+           "profile_rotamer": i32(B, N, T, fill=-1)}
+    if trace:
+        out["choice_trace"] = i32(B, sweeps, N, 2, fill=-1)
+    if B and N:
+        from . import full_atom
+        if rot is None:
+            tabs = [_table("rotamer_" + k, dev, lambda k=k: dict(zip(("chi", "count", "energy"), rotamer_table()))[k])
+                    for k in ("chi", "count", "energy")]
+        else:
+            tabs = [t.to(dev) for t in rot]
+        R = tabs[0].shape[1]
+        rigid, frames = full_atom._tables(dev)
+        if frames != [3, 4, 5, 6, 7]:
+            raise _capi.PepflowHipError(f"rigid_groups.npz: the frames are {frames}, the design kernel is written for [3, 4, 5, 6, 7]")
+        lib = _capi.load()
+        nbytes = lib.pf_sequence_design_work_bytes(B, N, R, SEQ_DESIGN_MAX_RES)
+        if nbytes < 0:
+            raise ValueError(f"design_sequence: the workspace for B = {B}, N = {N}, {R} rotamers exceeds 2 GiB; design the batch in parts")
+        ref = None if ref is None else ref.to(dev)
+        a = _capi.SeqDesignArgs()
+        _bind_in(a, pos=pos, atom_mask=atom_mask, aa=aa, residue_index=residue_index, designed=designed, candidates=cand, ref_energy=ref)
+        a.radius = _table("xs_radius", dev, xs_radius_table).data_ptr()
+        a.types = _table("interface_types", dev, interface_type_table).data_ptr()
+        a.own_mask = _table("pack_own_mask", dev, _pack_own_mask_table).data_ptr()
+        a.tab_rot, a.tab_trans, a.tab_group, a.tab_pos, a.tab_mask = (rigid[k].data_ptr() for k in ("rot", "trans", "group", "pos", "mask"))
+        a.rot_chi, a.rot_count, a.rot_energy = (t.data_ptr() for t in tabs)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        a.work = work.data_ptr()
+        names = {"aa": "aa_out", "pos": "pos_out", "atom_mask": "mask_out", "designed": "designed_out"}
+        _bind_out(a, {names.get(k, k): v for k, v in out.items()})
+        a.B, a.N, a.n_atoms, a.max_rot, a.max_res, a.sweeps, a.pro, a.cys = B, N, A, R, SEQ_DESIGN_MAX_RES, sweeps, _proline(), _cysteine()
+        a.cutoff = cutoff
+        a.w_gauss1, a.w_gauss2, a.w_repulsion, a.w_hydrophobic, a.w_hbond = w
+        _capi.check(lib.pf_sequence_design_fwd(C.byref(a), _capi.stream_ptr()), "pf_sequence_design_fwd")
+    _as_bool(out, "atom_mask", "designed")
+    return out
+
+
 # Guiding potentials of the sampler on their own (conventions and formulas: csrc/guidance.hip, include/pepflow_hip.h).  They stand
 # where RFdiffusion's guiding potentials stand, in role only: written from their formulas, checked against no other program.
 CA_POTENTIAL_MAX_L = _capi.GUIDE_MAX_L

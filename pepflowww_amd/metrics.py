@@ -22,7 +22,7 @@ the generated residues, an alanine scan and a position scan with the packer's se
 alignment identity across lengths and the nearest known sequence of a library (`sequence_scores`).
 
 Every per-residue, per-point and per-atom-pair operation runs in pf_superpose_fwd / pf_binding_site_fwd / pf_tm_score_fwd / pf_dssp_fwd /
-pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_polar_fwd / pf_relax_fwd / pf_cluster_fwd / pf_pack_sidechains_fwd / pf_mutation_scan_fwd / pf_seq_ratio_fwd / pf_seq_align_fwd / pf_seq_search_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
+pf_violations_fwd / pf_sasa_fwd / pf_torsions_fwd / pf_sidechain_compare_fwd / pf_lddt_fwd / pf_contacts_fwd / pf_interface_energy_fwd / pf_polar_fwd / pf_relax_fwd / pf_cluster_fwd / pf_pack_sidechains_fwd / pf_mutation_scan_fwd / pf_sequence_design_fwd / pf_seq_ratio_fwd / pf_seq_align_fwd / pf_seq_search_fwd (and the backbone reconstruction kernels); the host builds pair lists and masks and combines per-sample (or per-pair) outputs."""
 import ctypes as C
 import math
 
@@ -841,4 +841,53 @@ def mutation_scan(final, batch, backbone="packed", candidates="all", hot_spot=HO
     out["top_position"] = torch.where(found, torch.div(at, T, rounding_mode="floor"), torch.full_like(at, -1))
     out["top_type"] = torch.where(found, at % T, torch.full_like(at, -1))
     out["top_ddE"] = torch.where(found, v, torch.full_like(v, float("nan")))
+    return out
+
+
+def design_sequences(final, batch, backbone="frames", candidates="all", **kw):
+    """Fixed-backbone sequence design of each sample's generated residues against the fixed receptor on the device (geometry.
+    design_sequence: type and rotamer of every generated residue chosen together by iterated conditional modes over `pack_sidechains`'
+    energy).  It answers which sequence this package's own energy prefers on a sampled backbone, where the reference's evaluation
+    runs ProteinMPNN over the peptide chain of backbone-only samples (eval/run_mpnn.py: process_mpnn_bb, write_seq_to_pdb).  It is
+    NOT ProteinMPNN and NOT Rosetta fixbb and takes their place in role only: this package's Vina-form pair energy plus the rotamer
+    table's energy plus the caller's `ref_energy`, no solvation, no electrostatics, no entropy, no learned prior; without reference
+    energies it favours large side chains; a local search; the defaults are untuned and no reference energies are shipped.
+    final / batch and the sample's complex are those of `binding_energy` with backbone "frames" (the default: a backbone-only run) or
+    "full_atom"; designed = generate_mask & res_mask, the receptor is the fixed environment, the index comes from `residue_index`,
+    the types are where(generate, seqs, seqs_1).  candidates: "all", "ALA" or a sequence of three-letter names (a [20] set for every
+    designed residue); kw (ref_energy, rotamers, sweeps, cutoff, weights) goes to geometry.design_sequence.
+
+    -> dict of device tensors: seqs [B,L] int64 (the designed types; others as given); pos_heavyatom [B,L,15,3] float32 (the
+    receptor's atoms bit-identical to the rebuilt complex), mask_heavyatom [B,L,15] bool, chi [B,L,4], rotamer [B,L] int32 (-1 where
+    not designed), energy_trace [B,sweeps+1] float64, sweeps_run [B], profile [B,L,20] float32, status [B] int32 (1: more than
+    geometry.SEQ_DESIGN_MAX_RES generated residues, nothing designed); recovery_native, recovery_model [B] float64: the share of the
+    designed residues whose type equals seqs_1, final["seqs"] (NaN where nothing is designed); changed_from_model [B] int64: designed
+    residues whose type differs from final["seqs"]; energy_before, energy_after [B] float64 (geometry.interface_energy between
+    peptide and receptor) and clash_atoms_cross_before, clash_atoms_cross_after [B] int64 (the generated residues' atoms that
+    geometry.structural_violations flags against the receptor), on the complex as given and as designed."""
+    if backbone not in ("full_atom", "frames"):
+        raise ValueError(f"backbone must be 'full_atom' or 'frames', got {backbone!r}")
+    cand = _scan_candidate_mask(candidates)
+    if "trace" in kw:
+        raise ValueError("design_sequences does not return the choice trace; call geometry.design_sequence for it")
+    sweeps = kw.get("sweeps", 8)
+    if not isinstance(sweeps, int) or isinstance(sweeps, bool) or sweeps < 0:      # checked before final / batch are touched
+        raise ValueError(f"sweeps must be an integer >= 0, got {sweeps!r}")
+    geometry._ref_energy(kw.get("ref_energy"))
+    dev, res_mask, gen, index, (pos, mask, aa), (pos_n, mask_n, aa_n) = _complexes(final, batch, backbone, index=True)
+    mask = mask & res_mask[:, :, None]
+    r = geometry.design_sequence(pos, mask, aa, index, gen, candidates=cand, **kw)
+    new_mask = torch.where(r["designed"][:, :, None], r["atom_mask"], mask)
+    out = {"seqs": r["aa"], "pos_heavyatom": r["pos"], "mask_heavyatom": new_mask, "chi": r["chi"], "rotamer": r["rotamer"],
+           "energy_trace": r["energy_trace"], "sweeps_run": r["sweeps_run"], "profile": r["profile"], "status": r["status"]}
+    des = r["designed"]
+    count = des.sum(1).double()
+    model = final["seqs"].to(dev)
+    out["recovery_native"] = (des & (r["aa"] == aa_n)).sum(1).double() / count
+    out["recovery_model"] = (des & (r["aa"] == model)).sum(1).double() / count
+    out["changed_from_model"] = (des & (r["aa"] != model)).sum(1)
+    for tag, p, m, t in (("_before", pos, mask, aa), ("_after", r["pos"], new_mask, r["aa"])):
+        v = geometry.structural_violations(p, m, t, index, query=gen, group=gen)
+        out["clash_atoms_cross" + tag] = (v["clash_atom_cross"] & gen[:, :, None]).sum((1, 2))
+        out["energy" + tag] = geometry.interface_energy(p, m, t, gen)["energy"]
     return out
